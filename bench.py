@@ -5,7 +5,11 @@ A "step" is one incremental update() sweep of the hot path (decide -> relabel st
 statistics over every voxel -> band/density bookkeeping) over the synthetic volume.  Inputs are
 generated on the GPU with torch (plumbing only) and are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--shape 880x880x640]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--shape 880x880x640] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints its line.  --full adds what is measured beside the
+headline, each in runs of its own: the band chain alone, a re-init, the side lines (roofline_nomask, many_flip,
+refine_like) and cpu_baseline.  --dump-outputs DIR writes what the timed steps computed (dump_outputs).
 
 N > 1: one rank per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process is one
 rank; started plainly with --gpus N it starts the N ranks itself (a child `python -m torch.distributed.run`,
@@ -334,6 +338,56 @@ def cpu_baseline(I_t, vm_t, H, levels_note, min_free_gb=48.0, crop_vox=70e6):
             'reference_itself': REFERENCE_ITSELF}
 
 
+DUMP_LABEL_SAMPLE = 1 << 21    # voxels of the seeded label sample of --dump-outputs
+DUMP_SEG_ROWS = 1 << 19        # rows of `segmented` written in full; a longer list is sampled (seeded)
+DUMP_BAND_ROWS = 1 << 18       # rows of each band list written in full; a longer list is sampled (seeded)
+DUMP_SEED = 20240611
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(s, outdir, first_row):
+    """--dump-outputs: what the timed steps computed, as a caller of the session receives it after the last step, as float32 /
+    float64 .npy files (about 40 MB at 880x880x640):
+      labels_sample        labels 0..4 of a fixed seeded sample of voxels (float32); labels_sample_index: their flat indices
+                           into the (nx, ny, nz) C-order volume (float64)
+      labels_per_plane     voxels of each label 0..4 per Z plane, every voxel of the volume (float64, nz x 5)
+      segmented            the segmented list in its order, (x, y, z) rows (float32); above DUMP_SEG_ROWS rows a seeded sample
+                           of rows, in order, and segmented_index their positions (float64)
+      band_inner, band_outer
+                           the band lists in their order, rows (x, y, z, innerProb, outerProb) (float64); above DUMP_BAND_ROWS
+                           rows a seeded sample of rows, in order, and band_inner_index / band_outer_index their positions
+      trace                one row per timed step, the trace fields of TRACE_DTYPE in order (float64)
+    All of it stays under DUMP_MAX_BYTES (64 MB)."""
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    lab = s.labels()
+    flat = lab.reshape(-1)
+    idx = np.unique(rng.integers(0, flat.size, size=min(flat.size, DUMP_LABEL_SAMPLE), dtype=np.int64))
+    out = {'labels_sample': flat[idx].astype(np.float32), 'labels_sample_index': idx.astype(np.float64),
+           'labels_per_plane': np.stack([(lab == k).sum(axis=(0, 1)) for k in range(5)], axis=1).astype(np.float64)}
+    del lab, flat
+    seg = s.segmented()
+    if len(seg) > DUMP_SEG_ROWS:
+        rows = np.sort(rng.choice(len(seg), size=DUMP_SEG_ROWS, replace=False))
+        seg = seg[rows]
+        out['segmented_index'] = rows.astype(np.float64)
+    out['segmented'] = seg.astype(np.float32)
+    for which, name in ((0, 'band_inner'), (1, 'band_outer')):
+        co, ip, op = s.band(which)
+        band = np.concatenate([co.astype(np.float64), ip[:, None], op[:, None]], axis=1)
+        if len(band) > DUMP_BAND_ROWS:
+            rows = np.sort(rng.choice(len(band), size=DUMP_BAND_ROWS, replace=False))
+            band = band[rows]
+            out[name + '_index'] = rows.astype(np.float64)
+        out[name] = band
+    tr = s.trace()[first_row:]
+    out['trace'] = np.stack([tr[f].astype(np.float64) for f in tr.dtype.names], axis=1)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, 'outputs of {} bytes exceed the limit of {}'.format(total, DUMP_MAX_BYTES)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 # Test aid (tests/test_gpu_parity.py): VRG_BENCH_SHARE_GPU=1 puts every rank of --gpus N on GPU 0 - N processes on the one GPU of a test
 # box, so that the N-rank body of this file runs there; RCCL refuses two ranks on one device, so the change log travels over hipIpc or
 # host callbacks and torch.distributed runs on gloo.  Never a measurement.
@@ -399,8 +453,11 @@ def main():
     ap.add_argument('--H', type=float, default=2.25)
     ap.add_argument('--integer-values', action='store_true', help='the same volume with integer intensities 0..levels (as a scanner delivers them) and H / levels^2: the same run, '
                     'with the level of a voxel looked up directly instead of searched for')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-side-lines', action='store_true', help='skip the two extra workloads of the default line (roofline_nomask, many_flip)')
+    ap.add_argument('--full', action='store_true', help='also measure what lies beside the headline, in runs of its own: the band chain alone, '
+                    're-init, the side lines (roofline_nomask, many_flip, refine_like) and cpu_baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what they computed as DIR/<name>.npy (one GPU)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip cpu_baseline')
+    ap.add_argument('--no-side-lines', action='store_true', help='--full: skip the extra workloads (roofline_nomask, many_flip, refine_like)')
     ap.add_argument('--variant', type=int, default=0)
     ap.add_argument('--sweep-blocks', type=int, default=0)
     ap.add_argument('--prio-mode', type=int, default=-1)
@@ -451,6 +508,8 @@ def main():
         if not args.levels:
             raise SystemExit('--integer-values needs --levels > 0')
         args.H = args.H / float(args.levels) ** 2
+    if args.dump_outputs and (world > 1 or args.force_dist or args.refine_like):
+        raise SystemExit('--dump-outputs writes the one-GPU run of the headline workload only')
     if world > 1 or args.force_dist:
         import torch.distributed as dist
         from arterynetwork_amd import slabs
@@ -543,24 +602,27 @@ def main():
         'roofline': roofline(shape, shape[2], kern_ms, int(r.sweep_launches), load_traffic(shape, 1, args.storage16, None, dense_bytes), args.storage16, dense_bytes, st['dense_kernel']),
     }
     out['config']['engine'] = st                            # trips handed back to the host / array growth during the run
-    out['config'].update(s.chain_timing(args.H))
-    # init once more on the warm handle (labels set again): what a second volume of the same shape costs
-    s.set_option('dense_off', 0)
-    s.set_labels_ptr(vm.data_ptr(), np.uint8, [st_ for st_ in vm.stride()])
-    t0 = time.perf_counter()
-    s.init(args.H)
-    out['config']['reinit_seconds'] = round(time.perf_counter() - t0, 4)
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, args.warmup + 1)
+    if args.full:
+        out['config'].update(s.chain_timing(args.H))
+        # init once more on the warm handle (labels set again): what a second volume of the same shape costs
+        s.set_option('dense_off', 0)
+        s.set_labels_ptr(vm.data_ptr(), np.uint8, [st_ for st_ in vm.stride()])
+        t0 = time.perf_counter()
+        s.init(args.H)
+        out['config']['reinit_seconds'] = round(time.perf_counter() - t0, 4)
     s.close()
     if out['roofline'].get('traffic') is not None:
         out['roofline']['traffic_source'] = 'profiles/traffic.json@{} (rocprofv3 PMC passes of these kernel sources, FETCH_SIZE x 2 + WRITE_SIZE; not measured by this run)'.format(device_source_sha())
-    if not args.no_side_lines and args.shape == '880x880x640' and not (args.storage16 or args.no_brain_mask or args.tubes > 1):
+    if args.full and not args.no_side_lines and args.shape == '880x880x640' and not (args.storage16 or args.no_brain_mask or args.tubes > 1):
         del I, vm
         torch.cuda.empty_cache()
         out['roofline_nomask'] = side_line(shape, dev, args, configure, roofline, 'nomask')
         out['many_flip'] = side_line(shape, dev, args, configure, roofline, 'many_flip')
         out['refine_like'] = side_line(shape, dev, args, configure, roofline, 'refine_like')
         I, vm = phantoms.bench_volume_torch(shape, dev, levels=args.levels, brain_mask=not args.no_brain_mask, integer_values=args.integer_values)   # (the cpu_baseline's volume)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(I, vm, args.H, lev_note)
     print(json.dumps(out), flush=True)
 

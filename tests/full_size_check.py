@@ -5,7 +5,7 @@ default      880x880x640 (the headline size), the torch-generated bench volume, 
 --oracle3    the same volume, 100 sweeps, against the ORACLE at full size (all cores; ~25 GB of host memory, a few minutes):
              labels of all 495 616 000 voxels, both band list orders and densities, `segmented` order, whole trace
 --slabs W NXxNYxNZ SWEEPS
-             BASELINE configs[3]'s partition at full size on ONE GPU: W ranks (processes) share GPU 0, each recounts its own
+             BASELINE configs[3]'s partition at full size on ONE GPU: W ranks (processes; ranks in turn above MAX_RANK_PROCS) share GPU 0, each recounts its own
              Z-slab of the same bench volume (host-callback reduction over gloo); every rank's labels, `segmented` and
              integer trace must equal the single-process run, and the ranks' slab counts must add up to the incremental
              region sizes of every sweep
@@ -129,16 +129,51 @@ def label_digest(s, shape, dev):
     return hashlib.sha256(lab.permute(2, 1, 0).contiguous().cpu().numpy().tobytes()).hexdigest(), lab
 
 
-def slab_worker(rank, world, port, shape, sweeps, outdir):
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import torch.distributed as dist
-    from arterynetwork_amd import slabs
-    dev = torch.device('cuda', 0)                          # every rank on GPU 0
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+# Rank processes that share the one GPU at a time.  The suite keeps at most six processes with the GPU open at once: pytest,
+# this driver (which opens the GPU only after its rank processes have ended) and at most four ranks.  A larger group runs its
+# ranks one after another in this process (ranks_in_turn): each rank is a session of its own, and what a collective would hand
+# it is replayed from the others.
+MAX_RANK_PROCS = 4
+# Position of the sweep-count entry in the closing all-sum vector of a replicated vrg_run, counted from its end: the vector has
+# 3 x sweeps + 8 entries and the count is entry 3 x sweeps + 3 (arterynetwork_amd/csrc/vrg_repl.h, `v[3 * ns + 3] = (double)iter`).
+ALLSUM_ITER_FROM_END = -5
+
+
+def free_port():
+    import socket
+    with socket.socket() as sk:
+        sk.bind(('127.0.0.1', 0))
+        return sk.getsockname()[1]
+
+
+def spawn_ranks(flag, world, args, timeout=None):
+    """`world` rank processes (this file with `flag`), started before this process touches the GPU."""
+    import subprocess
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), flag, str(rk), str(world)] + [str(a) for a in args]) for rk in range(world)]
+    rcs = [p.wait(timeout=timeout) for p in procs]
+    assert all(rc == 0 for rc in rcs), rcs
+
+
+def ranks_in_turn(world, run_rank, first_guess):
+    """Every rank of a group, one after another.  run_rank(rank, reply) runs one rank and returns (result, inputs): `inputs` are the
+    vectors the rank handed to its collective, call by call, and reply(k, v) is what the collective returns for the k-th call.
+    Pass 1 replies first_guess(k, v); pass 2 replies the sum over the ranks of the pass-1 inputs - what the collective returns - and
+    has to see the same inputs again (so each rank ran exactly as in a group whose ranks run at once).  Returns the results."""
+    res, ins = zip(*[run_rank(rk, first_guess) for rk in range(world)])
+    ncall = {len(i) for i in ins}
+    assert len(ncall) == 1, 'ranks made different numbers of collective calls: %r' % ([len(i) for i in ins],)
+    totals = [np.sum(np.stack([np.asarray(i[k], np.float64) for i in ins]), axis=0) for k in range(ncall.pop())]
+    res2, ins2 = zip(*[run_rank(rk, lambda k, v: totals[k]) for rk in range(world)])
+    for rk in range(world):
+        assert len(ins2[rk]) == len(ins[rk]) and all(np.array_equal(a, b) for a, b in zip(ins2[rk], ins[rk])), \
+            'rank %d: inputs of its collectives changed once it got the sums' % rk
+    return res2
+
+
+def slab_rank(s, shape, sweeps, dev, seen):
+    """Body of one Z-slab rank: init + `sweeps` sweeps; what the parent compares."""
     I, vm = phantoms.bench_volume_torch(shape, dev)
     torch.cuda.synchronize()
-    seen = []
-    s = slabs.make_slab_session(shape, rank, world, device=0, reduce='callback', observer=lambda p, t: seen.append(p + t))
     s.set_option('batch', 16)
     s.set_volume_ptr(I.data_ptr(), np.float32, list(I.stride()))
     s.set_labels_ptr(vm.data_ptr(), np.uint8, list(vm.stride()))
@@ -146,18 +181,54 @@ def slab_worker(rank, world, port, shape, sweeps, outdir):
     r = s.run(sweeps, 10 ** 12, None)
     assert r.sweeps == sweeps, (r.sweeps, r.stop_reason)
     digest, _ = label_digest(s, shape, dev)
-    np.savez(os.path.join(outdir, 'rank%d.npz' % rank), digest=np.str_(digest), seg=s.segmented(), tr=s.trace(),
-             seen=np.asarray(seen, np.float64), slab=np.asarray(s.slab), dense_bytes=np.int64(s.stats()['dense_bytes']))
+    out = dict(digest=np.str_(digest), seg=s.segmented(), tr=s.trace(), seen=np.asarray(seen, np.float64), slab=np.asarray(s.slab),
+               dense_bytes=np.int64(s.stats()['dense_bytes']))
     s.close()
+    del I, vm
+    torch.cuda.empty_cache()
+    return out
+
+
+def slab_worker(rank, world, port, shape, sweeps, outdir):
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    import torch.distributed as dist
+    from arterynetwork_amd import slabs
+    dev = torch.device('cuda', 0)                          # every rank on GPU 0
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    seen = []
+    s = slabs.make_slab_session(shape, rank, world, device=0, reduce='callback', observer=lambda p, t: seen.append(p + t))
+    np.savez(os.path.join(outdir, 'rank%d.npz' % rank), **slab_rank(s, shape, sweeps, dev, seen))
     dist.barrier()
     dist.destroy_process_group()
 
 
+def slab_ranks_in_turn(world, shape, sweeps, dev, ref_tr):
+    """The Z-slab ranks one after another (ranks_in_turn); the first guess of the sums is the single-process run's region statistics."""
+    from arterynetwork_amd import slabs
+
+    def run_rank(rank, reply):
+        seen, ins = [], []
+
+        def allreduce(v):
+            ins.append(np.asarray(v, np.float64))
+            out = [float(x) for x in reply(len(ins) - 1, ins[-1])]
+            seen.append(list(v) + out)
+            return out
+        s = slabs.make_slab_session(shape, rank, world, device=0, reduce='none')
+        s.set_reduce_callback(allreduce)
+        return slab_rank(s, shape, sweeps, dev, seen), ins
+    guess = lambda k, v: [ref_tr['n_in'][k], ref_tr['n_out'][k], ref_tr['sum_in'][k], ref_tr['sum_out'][k]]
+    return ranks_in_turn(world, run_rank, guess)
+
+
 def slabs_one_gpu(world, shape, sweeps):
-    """Parent: the single-process run, then `world` rank processes on the same GPU; compare."""
-    import subprocess
+    """Parent: `world` rank processes on the same GPU (or, for a group larger than MAX_RANK_PROCS, its ranks in turn), and the
+    single-process run; compare."""
     import tempfile
-    import socket
+    in_turn = world > MAX_RANK_PROCS
+    if not in_turn:
+        outdir = tempfile.mkdtemp(prefix='slabs_')
+        spawn_ranks('--slab-worker', world, [free_port(), 'x'.join(map(str, shape)), sweeps, outdir])
     dev = torch.device('cuda', 0)
     I, vm = phantoms.bench_volume_torch(shape, dev, tubes=int(os.environ.get('VRG_CHECK_TUBES', '1')))     # (env: several tubes = thousands of flips per sweep)
     torch.cuda.synchronize()
@@ -173,19 +244,15 @@ def slabs_one_gpu(world, shape, sweeps):
     s.close()
     del I, vm
     torch.cuda.empty_cache()
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    outdir = tempfile.mkdtemp(prefix='slabs_')
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), '--slab-worker', str(rk), str(world), str(port),
-                               'x'.join(map(str, shape)), str(sweeps), outdir]) for rk in range(world)]
-    rcs = [p.wait() for p in procs]
-    assert all(rc == 0 for rc in rcs), rcs
+    if in_turn:
+        ranks = slab_ranks_in_turn(world, shape, sweeps, dev, ref_tr)
+    else:
+        ranks = [np.load(os.path.join(outdir, 'rank%d.npz' % rk)) for rk in range(world)]
     planes = []
     seen_sum = None
     nbytes = 0
     for rk in range(world):
-        z = np.load(os.path.join(outdir, 'rank%d.npz' % rk))
+        z = ranks[rk]
         assert str(z['digest']) == ref_digest, 'rank %d: labels differ from the single-process run' % rk
         assert np.array_equal(z['seg'], ref_seg), 'rank %d: segmented differs' % rk
         for f in ('nflip', 'nseg', 'n_in', 'n_out', 'ni', 'no', 'ties'):
@@ -205,21 +272,14 @@ def slabs_one_gpu(world, shape, sweeps):
     assert sum(planes) == shape[2] and max(planes) - min(planes) <= 1
     # the slabs' dense passes fetch what the single pass fetches, plus at most the two class-word units a face cuts
     assert ref_bytes <= nbytes <= ref_bytes + world * 2 * (256 + 4 * 1024 * 4)
-    print('SLABS OK: %s, %d ranks on one GPU (slabs of %s planes), %d sweeps: labels / segmented / trace identical on every rank, '
-          'slab counts add up every sweep (nseg %d -> %d)' % ('x'.join(map(str, shape)), world, sorted(set(planes)), sweeps, ref_tr['nseg'][0], ref_tr['nseg'][-1]))
+    print('SLABS OK: %s, %d ranks on one GPU%s (slabs of %s planes), %d sweeps: labels / segmented / trace identical on every rank, '
+          'slab counts add up every sweep (nseg %d -> %d)' % ('x'.join(map(str, shape)), world, ' (in turn)' if in_turn else '', sorted(set(planes)), sweeps, ref_tr['nseg'][0], ref_tr['nseg'][-1]))
 
 
-def replica_worker(rank, world, port, shape, sweeps, outdir, transport, leader_verifies):
-    """One rank of a leader / follower group, every rank on GPU 0 (own process, own HIP context)."""
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import torch.distributed as dist
-    from arterynetwork_amd import replica
-    dev = torch.device('cuda', 0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def replica_rank(s, shape, sweeps, dev, fault):
+    """Body of one rank of a leader / follower group: init + two vrg_run calls (the log goes on where the first ended)."""
     I, vm = phantoms.bench_volume_torch(shape, dev, tubes=int(os.environ.get('VRG_CHECK_TUBES', '1')))
     torch.cuda.synchronize()
-    fault = int(os.environ.get('VRG_CHECK_FAULT', '0'))     # (option repl_fault: a rank fails on the host side in the middle of the run - every rank must return an error)
-    s = replica.make_replica_session(shape, rank, world, device=0, transport=transport, leader_verifies=bool(leader_verifies), options={'batch': 16, 'repl_fault': fault})
     s.set_volume_ptr(I.data_ptr(), np.float32, list(I.stride()))
     s.set_labels_ptr(vm.data_ptr(), np.uint8, list(vm.stride()))
     s.init(2.25)
@@ -230,30 +290,94 @@ def replica_worker(rank, world, port, shape, sweeps, outdir, transport, leader_v
             s.run(sweeps, 10 ** 12, None)
         except VrgError as e:
             err = str(e)
-        np.savez(os.path.join(outdir, 'rank%d.npz' % rank), err=np.str_(err))
         s.close()
-        dist.barrier()
-        dist.destroy_process_group()
-        return
-    r = s.run(sweeps // 2, 10 ** 12, None)                  # two calls: the log goes on where the first run ended
+        return dict(err=np.str_(err))
+    r = s.run(sweeps // 2, 10 ** 12, None)
     r2 = s.run(sweeps, 10 ** 12, None)
     assert r.sweeps + r2.sweeps == sweeps, (r.sweeps, r2.sweeps, r2.stop_reason)
     digest, _ = label_digest(s, shape, dev)
     st = s.repl_stats()
-    np.savez(os.path.join(outdir, 'rank%d.npz' % rank), digest=np.str_(digest), seg=s.segmented(), tr=s.trace(), transport=np.str_(s.replica['transport']),
-             stats=np.array([st['batches'], st['records'], st['sweeps'], st['verified'], st['verifiers'], st['slot']], np.int64),
-             res=np.array([r2.stop_reason, r2.iter_num, r2.nseg, r2.n_in, r2.n_out, r2.ni, r2.no, r2.ties], np.int64))
+    out = dict(digest=np.str_(digest), seg=s.segmented(), tr=s.trace(), transport=np.str_(s.replica['transport']),
+               stats=np.array([st['batches'], st['records'], st['sweeps'], st['verified'], st['verifiers'], st['slot']], np.int64),
+               res=np.array([r2.stop_reason, r2.iter_num, r2.nseg, r2.n_in, r2.n_out, r2.ni, r2.no, r2.ties], np.int64))
     s.close()
+    del I, vm
+    torch.cuda.empty_cache()
+    return out
+
+
+def replica_worker(rank, world, port, shape, sweeps, outdir, transport, leader_verifies):
+    """One rank of a leader / follower group, every rank on GPU 0 (own process, own HIP context)."""
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    import torch.distributed as dist
+    from arterynetwork_amd import replica
+    dev = torch.device('cuda', 0)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    fault = int(os.environ.get('VRG_CHECK_FAULT', '0'))     # (option repl_fault: a rank fails on the host side in the middle of the run - every rank must return an error)
+    s = replica.make_replica_session(shape, rank, world, device=0, transport=transport, leader_verifies=bool(leader_verifies), options={'batch': 16, 'repl_fault': fault})
+    np.savez(os.path.join(outdir, 'rank%d.npz' % rank), **replica_rank(s, shape, sweeps, dev, fault))
     dist.barrier()
     dist.destroy_process_group()
 
 
+def replica_ranks_in_turn(world, shape, sweeps, dev, leader_verifies):
+    """The ranks of a leader / follower group one after another (ranks_in_turn): the leader's change log is recorded as it broadcasts
+    it (every broadcast has root 0) and played back to each follower; the closing all-sum of every vrg_run is the collective replayed.
+    Its first guess is the rank's own vector with the sweep-count entry (ALLSUM_ITER_FROM_END) scaled by the group size: every
+    rank ends on the same sweep.  Transport 'in-turn' of --replicas; no rank reads the log while the leader writes it."""
+    from arterynetwork_amd import replica
+    log = []
+
+    def run_rank(rank, reply):
+        ins = []
+        feed = iter(log)
+        if rank == 0:
+            del log[:]
+
+        def bcast(buf, root):
+            assert root == 0
+            if rank == 0:
+                log.append(bytes(buf))
+            else:
+                b = next(feed)
+                assert len(b) == len(buf)
+                np.frombuffer(buf, dtype=np.uint8)[:] = np.frombuffer(b, dtype=np.uint8)
+
+        def allsum(v):
+            ins.append(np.asarray(v, np.float64))
+            return [float(x) for x in reply(len(ins) - 1, ins[-1])]
+        s = replica.make_replica_session(shape, rank, world, device=0, transport='none', leader_verifies=bool(leader_verifies), options={'batch': 16})
+        s.repl_set_callbacks(bcast, allsum)
+        out = replica_rank(s, shape, sweeps, dev, 0)
+        if rank > 0:
+            assert next(feed, None) is None, 'rank %d: part of the change log was not consumed' % rank
+        return out, ins
+
+    def guess(k, v):
+        v = np.array(v)
+        v[ALLSUM_ITER_FROM_END] *= world
+        return v
+    return ranks_in_turn(world, run_rank, guess)
+
+
 def replicas_one_gpu(world, shape, sweeps, transport, leader_verifies):
-    """Parent: the single-process run, then `world` rank processes of a leader / follower group on the same GPU; every rank's
-    labels, `segmented` order, whole trace (intensity sums bit for bit) and result must equal the single process's."""
-    import subprocess
+    """Parent: `world` rank processes of a leader / follower group on the same GPU, the log over `transport` ('ipc' or 'callback'; at
+    most MAX_RANK_PROCS of them) - or, with transport 'in-turn', the ranks one after another in this process with the log recorded
+    and played back (replica_ranks_in_turn) - and the single-process run; every rank's labels, `segmented` order, whole trace
+    (intensity sums bit for bit) and result must equal the single process's."""
     import tempfile
-    import socket
+    fault = int(os.environ.get('VRG_CHECK_FAULT', '0'))
+    in_turn = transport == 'in-turn'
+    assert not (in_turn and fault), 'an injected fault needs the rank processes'
+    assert in_turn or world <= MAX_RANK_PROCS, '%d rank processes on one GPU: at most %d (MAX_RANK_PROCS); transport in-turn runs a larger group' % (world, MAX_RANK_PROCS)
+    if not in_turn:
+        outdir = tempfile.mkdtemp(prefix='replicas_')
+        spawn_ranks('--replica-worker', world, [free_port(), 'x'.join(map(str, shape)), sweeps, outdir, transport, int(leader_verifies)], timeout=600)
+    if fault:
+        errs = [str(np.load(os.path.join(outdir, 'rank%d.npz' % rk))['err']) for rk in range(world)]
+        assert all(errs), 'a rank returned without an error: %r' % (errs,)
+        print('REPLICAS FAIL TOGETHER: %d ranks on one GPU over %s, injected fault %s: every rank returned an error, none hung' % (world, transport, os.environ['VRG_CHECK_FAULT']))
+        return
     dev = torch.device('cuda', 0)
     I, vm = phantoms.bench_volume_torch(shape, dev, tubes=int(os.environ.get('VRG_CHECK_TUBES', '1')))     # (env: several tubes = thousands of flips per sweep)
     torch.cuda.synchronize()
@@ -270,23 +394,14 @@ def replicas_one_gpu(world, shape, sweeps, transport, leader_verifies):
     s.close()
     del I, vm
     torch.cuda.empty_cache()
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    outdir = tempfile.mkdtemp(prefix='replicas_')
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), '--replica-worker', str(rk), str(world), str(port),
-                               'x'.join(map(str, shape)), str(sweeps), outdir, transport, str(int(leader_verifies))]) for rk in range(world)]
-    rcs = [p.wait(timeout=600) for p in procs]
-    assert all(rc == 0 for rc in rcs), rcs
-    if int(os.environ.get('VRG_CHECK_FAULT', '0')):
-        errs = [str(np.load(os.path.join(outdir, 'rank%d.npz' % rk))['err']) for rk in range(world)]
-        assert all(errs), 'a rank returned without an error: %r' % (errs,)
-        print('REPLICAS FAIL TOGETHER: %d ranks on one GPU over %s, injected fault %s: every rank returned an error, none hung' % (world, transport, os.environ['VRG_CHECK_FAULT']))
-        return
+    if in_turn:
+        ranks, carried_by = replica_ranks_in_turn(world, shape, sweeps, dev, leader_verifies), 'none'     # (the sessions' own transport: none)
+    else:
+        ranks, carried_by = [np.load(os.path.join(outdir, 'rank%d.npz' % rk)) for rk in range(world)], transport
     counted = 0
     for rk in range(world):
-        z = np.load(os.path.join(outdir, 'rank%d.npz' % rk))
-        assert str(z['transport']) == transport, (rk, str(z['transport']))
+        z = ranks[rk]
+        assert str(z['transport']) == carried_by, (rk, str(z['transport']))
         assert str(z['digest']) == ref_digest, 'rank %d: labels differ from the single-process run' % rk
         assert np.array_equal(z['seg'], ref_seg), 'rank %d: segmented differs' % rk
         assert z['tr'].tobytes() == ref_tr.tobytes(), 'rank %d: trace differs (integer fields or the bits of the intensity sums)' % rk
@@ -298,7 +413,7 @@ def replicas_one_gpu(world, shape, sweeps, transport, leader_verifies):
             assert st[3] >= sweeps // st[4], (rk, st)                     # its share of the sweeps
     assert counted == (sweeps - (sweeps + world - 1) // world if leader_verifies else sweeps), (counted, sweeps)   # every sweep counted exactly once (the leader's share: sweeps 1, 1 + N, ...)
     print('REPLICAS OK: %s, %d ranks on one GPU over %s (leader %s), %d sweeps: labels / segmented / trace (sums bit for bit) / result identical '
-          'on every rank; the followers counted %d sweeps (nseg %d -> %d)' % ('x'.join(map(str, shape)), world, transport,
+          'on every rank; the followers counted %d sweeps (nseg %d -> %d)' % ('x'.join(map(str, shape)), world, transport if not in_turn else 'a recorded log played back, ranks in turn',
           'counts a share' if leader_verifies else 'only leads', sweeps, counted, ref_tr['nseg'][0], ref_tr['nseg'][-1]))
 
 

@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -89,3 +90,65 @@ def test_section8d_figure_is_kept_apart_from_frac():
     r = bench.roofline((880, 880, 640), 640, 0.178, 125, None, dense_bytes=1.0616e9, kernel='k_recount_bits<3,true,0,true>')
     assert r['kernel'] == 'k_recount_bits<3,true,0,true>' and 0.7 < r['frac'] < 0.8
     assert r['section8d_frac'] > 1.5 and 'not a fraction' in r['section8d_note']      # 6 B x voxels / time / peak: the driver's own figure
+
+
+def test_dump_outputs_of_the_timed_steps(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files of what the timed sweeps computed (sequential host model as compute); one trace
+    row per timed sweep, the label sample agrees with the labels, the same run writes the same files."""
+    from arterynetwork_amd._capi import Session, VrgLib
+    from test_slabs_gloo import HM, _inputs
+    import subprocess
+    subprocess.check_call(['make', '-C', os.path.join(ROOT, 'tests', 'hostmodel'), '-s', 'libvrg_hostmodel.so'])
+    data, vmap = _inputs()
+    got = []
+    for k in range(2):
+        s = Session(data.shape, lib=VrgLib(HM, 'vrgm_'))
+        s.set_volume(data); s.set_labels(vmap); s.init(2.25)
+        s.run(3, 10 ** 9, None)
+        s.run(8, 10 ** 9, None)
+        d = tmp_path / str(k)
+        bench.dump_outputs(s, str(d), 4)
+        lab, seg, tr = s.labels(), s.segmented(), s.trace()
+        bands = [s.band(0), s.band(1)]
+        s.close()
+        files = {p.stem: np.load(str(p)) for p in d.iterdir()}
+        assert sorted(files) == ['band_inner', 'band_outer', 'labels_per_plane', 'labels_sample', 'labels_sample_index', 'segmented', 'trace']
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= bench.DUMP_MAX_BYTES
+        assert np.array_equal(files['labels_sample'], lab.reshape(-1)[files['labels_sample_index'].astype(np.int64)])
+        assert files['labels_per_plane'].shape == (data.shape[2], 5)
+        assert np.array_equal(files['labels_per_plane'], np.stack([(lab == k).sum(axis=(0, 1)) for k in range(5)], axis=1))
+        assert np.array_equal(files['segmented'], seg.astype(np.float32))
+        assert files['trace'].shape == (5, len(tr.dtype.names))                     # the sweeps 4..8 of the second call
+        for j, f in enumerate(tr.dtype.names):
+            assert np.array_equal(files['trace'][:, j], tr[f][4:].astype(np.float64), equal_nan=True), f
+        for (co, ip, op), name in zip(bands, ('band_inner', 'band_outer')):
+            assert len(co) and np.array_equal(files[name], np.concatenate([co, ip[:, None], op[:, None]], axis=1))
+        got.append(files)
+    assert got[0].keys() == got[1].keys() and all(np.array_equal(got[0][n], got[1][n]) for n in got[0])
+
+
+def test_dump_outputs_samples_long_lists(tmp_path, monkeypatch):
+    """Lists longer than their caps are written as seeded samples of rows, in order, with the rows' positions beside them."""
+    from arterynetwork_amd._capi import Session, VrgLib
+    from test_slabs_gloo import HM, _inputs
+    data, vmap = _inputs()
+    monkeypatch.setattr(bench, 'DUMP_SEG_ROWS', 100)
+    monkeypatch.setattr(bench, 'DUMP_BAND_ROWS', 50)
+    s = Session(data.shape, lib=VrgLib(HM, 'vrgm_'))
+    s.set_volume(data); s.set_labels(vmap); s.init(2.25)
+    s.run(8, 10 ** 9, None)
+    bench.dump_outputs(s, str(tmp_path), 1)
+    seg, bands = s.segmented(), [s.band(0), s.band(1)]
+    s.close()
+    f = {p.stem: np.load(str(p)) for p in tmp_path.iterdir()}
+    rows = f['segmented_index'].astype(np.int64)
+    assert len(seg) > 100 and len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(f['segmented'], seg[rows].astype(np.float32))
+    for (co, ip, op), name in zip(bands, ('band_inner', 'band_outer')):
+        full = np.concatenate([co, ip[:, None], op[:, None]], axis=1)
+        if len(full) > 50:
+            rows = f[name + '_index'].astype(np.int64)
+            assert len(rows) == 50 and np.all(np.diff(rows) > 0) and np.array_equal(f[name], full[rows])
+        else:
+            assert np.array_equal(f[name], full)

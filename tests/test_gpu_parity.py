@@ -1051,11 +1051,15 @@ def test_drop_in_messages_and_trace(golden_loader, capsys):
 
 @pytest.mark.parametrize('shape,sweeps', [('880x880x640', 40), ('512x512x170', 40)])
 def test_config4_partition_8_ranks_one_gpu(shape, sweeps):
-    """BASELINE configs[3]'s partition at FULL size on the one GPU of the box: 8 rank processes share GPU 0, each recounts
-    its own Z-slab of the bench volume (880x880x640: 80 planes each, plane = 896 x 884 voxels against 1024-voxel units;
-    512x512x170: uneven slabs of 22 / 21 planes), host-callback reduction over gloo.  Every rank's labels, `segmented`
-    and integer trace equal the single-process run; the ranks' slab counts add up to the incremental region sizes of
-    every sweep.  (tests/full_size_check.py --slabs, own processes.)"""
+    """BASELINE configs[3]'s partition at FULL size on the one GPU of the box: 8 ranks on GPU 0, each recounts its own
+    Z-slab of the bench volume (880x880x640: 80 planes each, plane = 896 x 884 voxels against 1024-voxel units;
+    512x512x170: uneven slabs of 22 / 21 planes).  Every rank's labels, `segmented` and integer trace equal the
+    single-process run; the ranks' slab counts add up to the incremental region sizes of every sweep.
+    The 8 ranks run one after another in one process (tests/full_size_check.py --slabs; the suite keeps at most
+    MAX_RANK_PROCS rank processes on the GPU at once): each rank's reduction callback is answered with the sum of every
+    rank's partials, and a second pass checks that no rank's partials change once it gets those sums - so every rank
+    computes what it would in a group whose ranks run at once.  No gloo here: the reduction over gloo between rank
+    processes is test_zslabs_processes_one_gpu's."""
     import subprocess, sys, os
     from conftest import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'full_size_check.py'), '--slabs', '8', shape, str(sweeps)],
@@ -1064,14 +1068,17 @@ def test_config4_partition_8_ranks_one_gpu(shape, sweeps):
 
 
 @pytest.mark.parametrize('world,shape,sweeps,transport,leader_verifies,tubes', [
-    (8, '880x880x640', 40, 'ipc', 0, 1), (3, '512x512x170', 30, 'ipc', 1, 1), (4, '512x512x170', 30, 'callback', 0, 1),
-    (3, '256x192x96', 24, 'ipc', 0, 48)])            # (48 tubes: 4 800 flips per sweep - the four-launch chain's log, tens of thousands of records per sweep)
+    (4, '880x880x640', 40, 'ipc', 0, 1), (8, '880x880x640', 40, 'in-turn', 0, 1), (3, '512x512x170', 30, 'ipc', 1, 1),
+    (4, '512x512x170', 30, 'callback', 0, 1), (3, '256x192x96', 24, 'ipc', 0, 48)])            # (48 tubes: 4 800 flips per sweep - the four-launch chain's log, tens of thousands of records per sweep)
 def test_replicas_n_ranks_one_gpu(world, shape, sweeps, transport, leader_verifies, tubes):
     """Leader / follower replication (BASELINE configs[3] re-partitioned) at FULL size on the one GPU of the
-    box: `world` rank processes share GPU 0; the leader runs the band chain and logs every sweep, the followers map its log
-    buffers (hipIpc - the transport ranks of one node use between GPUs) or receive them through gloo callbacks, apply them and
-    count their share of the sweeps over the whole volume.  Every rank's labels, `segmented` order, whole trace - the intensity
-    sums bit for bit - and result equal the single-process run.  (tests/full_size_check.py --replicas, own processes.)"""
+    box: `world` rank processes share GPU 0 (at most MAX_RANK_PROCS of tests/full_size_check.py); the leader runs the band chain and
+    logs every sweep, the followers map its log buffers while it writes them (hipIpc - the transport ranks of one node use between
+    GPUs) or receive them through gloo callbacks, apply them and count their share of the sweeps over the whole volume.
+    Transport 'in-turn' (the 8-rank group): no rank processes and no transport - the ranks run one after another in one process,
+    the leader's log recorded and played back to each follower and the closing all-sum replayed (checked by a second pass); it
+    covers an 8-rank group's roles and shares, not hipIpc.  Every rank's labels, `segmented` order, whole trace - the intensity sums
+    bit for bit - and result equal the single-process run.  (tests/full_size_check.py --replicas.)"""
     import subprocess, sys, os
     from conftest import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'full_size_check.py'), '--replicas', str(world), shape, str(sweeps), transport, str(leader_verifies)],
@@ -1160,15 +1167,17 @@ def _rccl_replica_worker(rank, world, port, sweeps, outdir, leader_verifies):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('world,leader_verifies', [(2, True), (2, False), (4, True), (4, False), (8, True), (8, False)])
+# (each group size in the role replica.leader_verifies_default gives it; the other role of each size runs over gloo callbacks on CPU,
+# tests/test_replica_gloo.py, and over RCCL with one rank, test_replica_rccl_single_rank)
+@pytest.mark.parametrize('world,leader_verifies', [(2, True), (4, False), (8, False)])
 def test_replica_rccl_world_n(lib, tmp_path, world, leader_verifies):
     """RCCL with MORE THAN ONE rank: `world` processes, one GPU each, the change log streamed sweep by sweep over ncclBroadcast (xGMI
-    between the GPUs), the leader counting a share (leader_verifies) or only leading - the 8-rank configuration.  Every rank's labels,
+    between the GPUs), the leader counting a share (2 ranks) or only leading (4 and 8 ranks: the 8-rank configuration).  Every rank's labels,
     `segmented` order and trace equal the single-process run (the sums bit for bit where somebody counted the sweep).
     Skipped where fewer than `world` GPUs are visible (the driver's multi-GPU node runs it)."""
     import torch
     if torch.cuda.device_count() < world:
-        pytest.skip('needs {} GPUs'.format(world))
+        pytest.skip('needs {} GPUs, found {}'.format(world, torch.cuda.device_count()))
     import torch.multiprocessing as mp
     from test_slabs_gloo import free_port
     from arterynetwork_amd import phantoms

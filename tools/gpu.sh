@@ -29,7 +29,7 @@ except Exception as e:
     print(sys.argv[1], 'FAILED', e)
 PY
 }
-run() { name=$1; shift; timeout 900 python bench.py "$@" 2> "$out/bench_$name.err" | grep '^{' > "$out/bench_$name.json"; summ "$out/bench_$name.json"; }
+run() { name=$1; shift; timeout 900 python bench.py --full "$@" 2> "$out/bench_$name.err" | grep '^{' > "$out/bench_$name.json"; summ "$out/bench_$name.json"; }
 manyflip() { for sh in 512x512x170 880x880x640; do timeout 900 python tools/manyflip.py $sh 1,16,64,128,512 --sweeps 60 2>/dev/null | grep '^{' >> "$out/manyflip_$sh.jsonl"; done; python3 - "$out" <<'PY'
 import json, sys, glob
 for f in sorted(glob.glob(sys.argv[1] + '/manyflip_*.jsonl')):
@@ -80,7 +80,7 @@ for step in "$@"; do
           echo "---- $lib" >> "$out/fenced_ab.log"
           ( export VRG_HIP_LIB=$PWD/arterynetwork_amd/csrc/$lib
             timeout 1500 python tests/fuzz_gpu.py 2500 250 60000 2>&1 | grep -v amdgpu.ids | tail -3 >> "$out/fenced_ab.log"
-            timeout 600 python bench.py --shape 512x512x170 --steps 300 --no-cpu-baseline --no-side-lines 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('512x512x170: ms/step', d['ms_per_step'], 'band chain alone', d['config'].get('band_chain_ms'), 'dense', d['config'].get('dense_ms'))" >> "$out/fenced_ab.log" )
+            timeout 600 python bench.py --full --shape 512x512x170 --steps 300 --no-cpu-baseline --no-side-lines 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('512x512x170: ms/step', d['ms_per_step'], 'band chain alone', d['config'].get('band_chain_ms'), 'dense', d['config'].get('dense_ms'))" >> "$out/fenced_ab.log" )
         done
         ( export VRG_HIP_LIB=$PWD/arterynetwork_amd/csrc/libvrg_hip_fenced.so
           timeout 2400 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "many_flip or refine_like or kinds or replica or n_rank or stepwise or golden" 2>&1 | grep -E "passed|failed|error" | tail -3 | cut -c1-200 >> "$out/fenced_ab.log" )

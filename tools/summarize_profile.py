@@ -46,7 +46,7 @@ if st:
         a[0] += int(r['Calls']); a[1] += int(r['TotalDurationNs'])
     tot = sum(a[1] for a in agg.values())
     with open('profiles/%s_kernel_stats.csv' % name, 'w') as f:
-        f.write('# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline (%s)\n' % 'x'.join(map(str, shape)))
+        f.write('# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-side-lines (%s)\n' % 'x'.join(map(str, shape)))
         f.write('Name,Calls,TotalDurationNs,AverageNs,Percentage\n')
         for k, a in sorted(agg.items(), key=lambda kv: -kv[1][1]):
             f.write('"%s",%d,%d,%.1f,%.3f\n' % (k, a[0], a[1], a[1] / a[0], 100.0 * a[1] / tot))
@@ -70,7 +70,7 @@ for d in sorted(glob.glob(src + '/pmc_*')):
         rows.append((os.path.basename(d)[4:], kn, cn, m, len(core)))
         per[(kn, cn)] = m
 with open('profiles/%s_pmc.csv' % name, 'w') as f:
-    f.write('# rocprofv3 --pmc <set> -- python3 bench.py --steps 30 --warmup 10 --no-cpu-baseline --serial 1 ...: one run per counter set; mean per launch\n')
+    f.write('# rocprofv3 --pmc <set> -- python3 bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-side-lines --serial 1 ...: one run per counter set; mean per launch\n')
     f.write('pass,kernel,counter,mean_per_launch,launches_used\n')
     for r in rows:
         f.write('%s,%s,%s,%.1f,%d\n' % r)
