@@ -1,6 +1,6 @@
 // vrg_backend.h - what vrg_engine.cpp needs from an execution backend.
 //
-// The product backend is vrg_device.hip (HIP kernels on gfx950).  tests/hostmodel/ implements the
+// The product backend is vrg_chain.hip, vrg_device.hip, vrg_init.hip and vrg_follow.hip (HIP kernels on gfx950; vrg_device.h).  tests/hostmodel/ implements the
 // same interface with sequential loops over the very same item functions (vrg_items.h) so that the
 // parallel restatement of the reference's sequential update() can be checked against the oracle
 // without a GPU; that model is test infrastructure and is never linked into the product library.

@@ -1,5 +1,5 @@
 // vrg_engine.cpp - handle management and the C-ABI entry points (include/vrg.h) on top of a backend.
-// Compiled with hipcc into libvrg_hip.so (backend vrg_device.hip).  tests/hostmodel compiles the same
+// Compiled with hipcc into libvrg_hip.so (backend vrg_device.h: vrg_chain.hip, vrg_device.hip, vrg_init.hip, vrg_follow.hip).  tests/hostmodel compiles the same
 // file with VRG_API_PREFIX=vrgm_ against the sequential test backend.
 #include <algorithm>
 #include <chrono>

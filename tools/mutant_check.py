@@ -7,7 +7,8 @@ caught (the recount's cross-check against the incremental sizes raises VRG_E_INT
 product build's)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'arterynetwork_amd', 'csrc')
+sys.path.insert(0, ROOT)
+from arterynetwork_amd import build as B
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 
 CHILD = r'''
@@ -43,27 +44,15 @@ for r in range(%d):
 print('RESULT caught', caught, 'clean', clean, 'other errors', other)
 '''
 
-def build(name, flags):
-    out = os.path.join(CSRC, name)
-    srcs = [os.path.join(CSRC, f) for f in ('vrg_device.hip', 'vmask_device.hip', 'vrg_items.h', 'vrg_types.h', 'vrg_backend.h', 'vrg_repl.h', 'vrg_engine.cpp')]
-    srcs += [os.path.join(ROOT, 'include', f) for f in ('vrg.h', 'vmask.h')]
-    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(f) for f in srcs):
-        return out                                      # (built where the sources were edited: the library travels with the tree)
-    # (to a temporary name, moved into place on success: a failed compile never leaves a stale library with an older VrgCtx layout behind)
-    p = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared'] + flags + ['-o', out + '.tmp',
-                        'vrg_device.hip', 'vrg_engine.cpp', 'vmask_device.hip', '-L/opt/rocm/lib', '-lrccl'], cwd=CSRC, capture_output=True, text=True)
-    if p.returncode != 0:
-        for f in (out, out + '.tmp'):
-            if os.path.exists(f): os.remove(f)
-        raise SystemExit('mutant_check: %s did not compile:\n%s' % (name, p.stderr[-3000:]))
-    os.replace(out + '.tmp', out)
-    return out
+def build(name, defines):
+    # (rebuilt only when a source is newer: the library travels with the tree)
+    return B.build(out=name, defines=defines)
 
 if len(sys.argv) > 2 and sys.argv[2] == 'build-only':
-    build('libvrg_hip_mutant.so', ['-DVRG_MUTANT']); build('libvrg_hip_mutant_chaos.so', ['-DVRG_MUTANT', '-DVRG_CHAOS'])
+    build('libvrg_hip_mutant.so', ['VRG_MUTANT']); build('libvrg_hip_mutant_chaos.so', ['VRG_MUTANT', 'VRG_CHAOS'])
     raise SystemExit(0)
-for label, name, flags in (('product build', None, None), ('mutant, quiet', 'libvrg_hip_mutant.so', ['-DVRG_MUTANT']),
-                           ('mutant + random delays', 'libvrg_hip_mutant_chaos.so', ['-DVRG_MUTANT', '-DVRG_CHAOS'])):
+for label, name, flags in (('product build', None, None), ('mutant, quiet', 'libvrg_hip_mutant.so', ['VRG_MUTANT']),
+                           ('mutant + random delays', 'libvrg_hip_mutant_chaos.so', ['VRG_MUTANT', 'VRG_CHAOS'])):
     env = dict(os.environ, VRG_MUTANT_REF='/tmp/vrg_mutant_ref.txt')
     if not name and os.path.exists(env['VRG_MUTANT_REF']):
         os.remove(env['VRG_MUTANT_REF'])
