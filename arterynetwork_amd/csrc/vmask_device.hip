@@ -26,6 +26,7 @@
 
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
+#include "vmask_common.h"
 
 namespace {
 
@@ -601,6 +602,12 @@ template <class T> int vessel_mask_impl(const uint8_t* dbrain, const T* dves, Di
 }
 
 }  // namespace
+
+namespace vmask {                                  // (vmask_common.h: for vskel_device.hip)
+void set_error(const std::string& msg) { g_err = msg; }
+bool is_device_pointer(const void* p) { return is_dev(p); }
+int check_args(int device, int64_t n0, int64_t n1, int64_t n2) { Dims d; return check(device, n0, n1, n2, d); }
+}  // namespace vmask
 
 extern "C" {
 

@@ -9,6 +9,8 @@
  *                                                                       generateVesselVolume.py:107-136 (labelVolume),
  *                                                                       skeletonization.py:108
  *   vmask_vessel_mask  the threshold / component-size pipeline of       generateVesselVolume.py:187-199
+ *   vmask_skeleton     the curve skeleton that skeletonization.py:148-162 gets from an external tool and saves as
+ *                      skeleton.nii.gz (:783-790); here: subfield-sequential thinning, DESIGN.md section 9
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -41,6 +43,11 @@ int vmask_label(int device, const uint8_t* volume, int64_t n0, int64_t n1, int64
 int vmask_vessel_mask(int device, const uint8_t* brainMask, const void* vesselness, int dtype,
                       int64_t n0, int64_t n1, int64_t n2, double edt_max, double frac1, double frac2,
                       int64_t min_size, uint8_t* out, int64_t* kept);
+
+/* Curve skeleton of volume != 0 by subfield-sequential thinning.  out: uint8 0/1.
+ * *kept = voxels left, *cycles = cycles run (either may be NULL). */
+int vmask_skeleton(int device, const uint8_t* volume, int64_t n0, int64_t n1, int64_t n2,
+                   uint8_t* out, int64_t* kept, int64_t* cycles);
 
 const char* vmask_last_error(void);
 
