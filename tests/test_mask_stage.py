@@ -38,7 +38,8 @@ def test_oracle_pipeline_properties():
 @pytest.mark.parametrize('shape', [(40, 36, 30), (17, 64, 9), (1, 50, 33), (96, 80, 72), (3, 700, 5), (2, 6, 900), (130, 150, 140),
                                    (37, 9, 7), (70, 5, 6),       # (rows of 63 / 30 voxels: the axis-0 scans one column per thread, whole batches + a tail)
                                    (2, 3, 20000), (2, 20000, 3), # (the longest lines of the 32-bit envelope pass: quotients near 2^15, numerators near 2^30)
-                                   (2, 5, 23200)])      # (squared diagonal >= 2^29: the envelope pass in 64-bit arithmetic)
+                                   (2, 5, 23200),       # (squared diagonal >= 2^29: the envelope pass in 64-bit arithmetic)
+                                   (20000, 3, 2), (20011, 3, 2)])      # (a long axis 0: the scans run hundreds of whole batches of 32 / 16 rows; 20011: and a tail of 11)
 def test_edt_bit_exact(shape):
     from arterynetwork_amd.generateVesselVolume import distance_transform_edt
     brain, _ = _volumes(1, shape)

@@ -108,6 +108,10 @@ GPU_CASES['vessel-96x80x72'] = functools.partial(_vessel, 5, (96, 80, 72))
 GPU_CASES['phantom-48x40x32'] = M.crossing_phantom
 GPU_CASES['phantom-47x41x33'] = functools.partial(M.crossing_phantom, (47, 41, 33))
 GPU_CASES['empty-4x5x6'] = functools.partial(np.zeros, (4, 5, 6), np.uint8)
+# 260 * 260 * ceil(5 / 64) = 67 600 items of one wave each, more than the 16384 blocks x 4 waves = 65 536 that the whole-volume
+# kernels (pad, mark, unpad) launch at most: their grid-stride loops take a second turn.  Thin along i2 so that the object, about
+# 100 000 voxels, stays under the cap below and the sequential model stays affordable.
+GPU_CASES['random0.3-260x260x5'] = functools.partial(_random, (260, 260, 5), 0.3, 16)
 
 
 @pytest.mark.gpu
