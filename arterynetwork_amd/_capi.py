@@ -295,13 +295,20 @@ class Session:
 
     def stats(self):
         """Diagnostics: how often a trip was handed back to the host and why, array capacities."""
-        a = (C.c_int64 * 23)()
-        self._check(self.lib.get_stats(self._h, a, 23))
+        a = (C.c_int64 * 26)()
+        self._check(self.lib.get_stats(self._h, a, 26))
+        if a[14]:
+            dense_kernel = 'k_recount_pipe<3,{}>'.format('true' if a[9] else 'false')
+        else:
+            dense_kernel = 'k_recount_bits<{},{},{},{}>'.format(2 if a[10] == 2 else 3, 'true' if a[9] else 'false', a[10], 'true' if a[12] else 'false')
         return {'bail_flips': a[1], 'grow_marks': a[2], 'grow_pool': a[3], 'host_driven_trips': a[4],
                 'fused_trips': a[15], 'bail_fuse': a[16], 'density_bins': a[17], 'memo_trips': a[18],
                 'data_nonzero': a[19], 'slow_flips': a[22], 'bin_bytes': a[20], 'level_index_bytes': a[21], 'pool_capacity': a[5], 'mark_capacity': a[6], 'pool_slots': a[7], 'dense_bytes': a[8],
-                'dense_kernel': ('k_recount_pipe<3,{}>'.format('true' if a[9] else 'false') if a[14] else
-                                 'k_recount_bits<{},{},{},{}>'.format(2 if a[10] == 2 else 3, 'true' if a[9] else 'false', a[10], 'true' if a[12] else 'false')),
+                'dense_kernel': dense_kernel,
+                # what the dense pass streams per voxel, and who chose it: option storage16 (-1 automatic, 0 never, 1 always) and, in automatic
+                # mode, the decision of the last vrg_init (None where the option decided)
+                'dense_storage': {0: 'fp32 (4 B/voxel)', 1: 'u16 level index (2 B/voxel)', 2: 'float64 (8 B/voxel)', 3: 'u16 level index (2 B/voxel)'}.get(a[10]),
+                'storage16_option': a[23], 'storage16_auto': None if a[24] < 0 else bool(a[24]), 'level_index_builds': a[25],
                 'dense_nt_loads': bool(a[9]), 'dense_workgroups': a[11], 'dense_listed_units': a[13]}
 
     def nlevels(self):

@@ -65,8 +65,14 @@ struct vrg_handle {
     uint32_t nb_alloc = 0;
     int fused = 1;                       // option "fused": sweeps with few flips run update() as ONE launch (k_sweep)
     bool fuse_mode = false;              // ... and the trips being enqueued now are of that kind
-    int variant = 0, batch = 8, storage16 = 0, dense_off = 0;
-    uint16_t* lev16_buf = nullptr;
+    int variant = 0, batch = 8, dense_off = 0;
+    int storage16 = -1;                  // option "storage16": -1 automatic (by the volume's size and its level table), 0 never, 1 always
+    int64_t narrow_above = 300ll << 20;  // option "narrow_above": automatic 16-bit storage when the padded volume at its stored width is larger than this many bytes
+                                         // (the dense pass's nt_loads threshold: below it the pass comes out of the Infinity Cache and the band chain bounds the step)
+    int storage_auto = -1;               // what the last vrg_init decided: 1 / 0 = automatic mode chose 16-bit storage / kept the stored type, -1 = the option decided
+    uint16_t* lev16_buf = nullptr; bool lev16_valid = false;   // 16-bit level-index volume (VrgCtx::lev16); kept across re-inits of the same volume
+    long long lev16_builds = 0;          // how often it was built (be_build_lev16) since the handle was created
+    int narrow_alloc_fault = 0;          // option "narrow_alloc_fault" (tests): the index volume's allocation fails
     uint32_t* lidx_buf = nullptr; bool lidx_valid = false;   // per-voxel level index of a large level table (VrgCtx::lidx)
     float* I32 = nullptr; double* I64 = nullptr;
     uint64_t band_capacity = 0;
@@ -103,6 +109,14 @@ void release(vrg_handle* h, void* p) {
     auto it = std::find(h->owned.begin(), h->owned.end(), p);
     if (it != h->owned.end()) h->owned.erase(it);
     be_free(h->be, p);
+}
+// the 16-bit level-index volume: allocated on first use, padding zeroed (level 0 is always a valid index)
+bool ensure_lev16_buf(vrg_handle* h) {
+    if (h->lev16_buf) return true;
+    if (h->narrow_alloc_fault) return false;
+    h->lev16_buf = alloc<uint16_t>(h, h->PVu); h->lev16_valid = false;
+    if (h->lev16_buf) be_fill(h->be, h->lev16_buf, 0, h->PVu * 2);
+    return h->lev16_buf != nullptr;
 }
 uint64_t pow2_at_least(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 
@@ -368,7 +382,9 @@ int API(set_option)(vrg_handle* h, const char* name, int64_t value) {
     else if (n == "verify_every") { if (value < 0) return fail(h, VRG_E_ARG, "verify_every: 0 (never), 1 (every sweep: the default) or n > 1 (every n-th sweep)"); h->verify_every = (int)std::min<int64_t>(value, 1 << 20); be_set_tuning(h->be, name, value); }
     else if (n == "open_sweeps" || n == "mark_compact" || n == "band_blocks_max") be_set_tuning(h->be, name, value);
     else if (n == "sweep_blocks" || n == "prio_mode" || n == "small_flips" || n == "fuse_max" || n == "memo_above" || n == "serial_streams" || n == "skip_excluded" || n == "nt_loads" || n == "dense_pipe") be_set_tuning(h->be, name, value);
-    else if (n == "storage16") h->storage16 = value != 0;      // takes effect at the next vrg_init
+    else if (n == "storage16") h->storage16 = value < 0 ? -1 : (value != 0);      // takes effect at the next vrg_init
+    else if (n == "narrow_alloc_fault") h->narrow_alloc_fault = value != 0;   // tests: the 2 B/voxel buffer cannot be allocated (automatic mode keeps the stored type; storage16 = 1 fails)
+    else if (n == "narrow_above") { if (value < 0) return fail(h, VRG_E_ARG, "narrow_above: a number of bytes >= 0"); h->narrow_above = value; }   // ... as does this
     else if (n == "repl_fault") h->repl.fault = value;             // tests: a host-side failure in the middle of a replicated run (every rank must return an error, none may hang)
     else if (n == "repl_chunk") h->repl.chunk_min = value;
     else if (n == "repl_stream") h->repl.stream = value != 0;      // any time between runs: 1 (default) the change log travels sweep by sweep; 0: once per batch of trips
@@ -393,6 +409,7 @@ int API(set_volume)(vrg_handle* h, const void* data, int dtype, const int64_t st
         c.I = nullptr; c.I64 = h->I64;
     } else { c.I = h->I32; c.I64 = nullptr; }
     h->have_vol = true; h->inited = false;
+    h->lev16_valid = false;                          // (the level indices describe the volume that was here before)
     if (c.lev) {                                     // distinct-value table and its arrays are rebuilt by the next vrg_init
         release(h, (void*)c.lev); c.lev = nullptr;
         if (c.lev_map) { release(h, (void*)c.lev_map); c.lev_map = nullptr; }
@@ -491,17 +508,26 @@ int API(init)(vrg_handle* h, double H) {
         }
     }
     c.lev16 = nullptr; c.lidx = nullptr;
-    if (!h->storage16 && L > (uint32_t)VRG_KTAB_LEVELS) {   // large level table: every voxel's level index once, instead of a search whenever a voxel enters the band
+    // 16-bit storage: asked for (1: more than 16384 levels is an error), or chosen here (-1) - from whole-volume quantities only (padded voxels, levels,
+    // stored type), so that every rank of a slab or replica group decides alike; the automatic choice never fails an init: it keeps the stored type instead
+    bool narrow = h->storage16 > 0;
+    h->storage_auto = -1;
+    if (h->storage16 < 0) {
+        narrow = L <= 16384 && (uint64_t)c.PV * (c.I ? 4u : 8u) > (uint64_t)h->narrow_above;
+        if (narrow && !ensure_lev16_buf(h)) narrow = false;
+        h->storage_auto = narrow ? 1 : 0;
+    }
+    if (!narrow && h->lev16_buf) { release(h, h->lev16_buf); h->lev16_buf = nullptr; h->lev16_valid = false; }   // (2 B per padded voxel nobody reads)
+    if (!narrow && L > (uint32_t)VRG_KTAB_LEVELS) {   // large level table: every voxel's level index once, instead of a search whenever a voxel enters the band
         if (!h->lidx_buf) h->lidx_buf = alloc<uint32_t>(h, h->PVu);
         if (!h->lidx_buf) return fail(h, VRG_E_MEM, "vrg_init: level-index volume");
         if (!h->lidx_valid) { be_build_lidx(be, c, h->lidx_buf); h->lidx_valid = true; }
         c.lidx = h->lidx_buf;
     }
-    if (h->storage16) {                             // 16-bit intensity storage: level indices + LDS value table
+    if (narrow) {                                   // 16-bit intensity storage: level indices + LDS value table
         if (L > 16384) return fail(h, VRG_E_ARG, "storage16: more than 16384 distinct intensity values");
-        if (!h->lev16_buf) h->lev16_buf = alloc<uint16_t>(h, h->PVu);
-        if (!h->lev16_buf) return fail(h, VRG_E_MEM, "vrg_init: 16-bit level volume");
-        be_build_lev16(be, c, h->lev16_buf);
+        if (!ensure_lev16_buf(h)) return fail(h, VRG_E_MEM, "vrg_init: 16-bit level volume");
+        if (!h->lev16_valid) { be_build_lev16(be, c, h->lev16_buf); h->lev16_valid = true; h->lev16_builds++; }   // (built once per volume: set_volume invalidates it)
         c.lev16 = h->lev16_buf;
     }
     c.lab[1] = nullptr;
@@ -834,6 +860,8 @@ int API(get_stats)(vrg_handle* h, int64_t* outp, int64_t cap) {
         outp[9] = di[0]; outp[10] = di[1]; outp[11] = di[2]; outp[12] = di[3]; outp[13] = uc[0];
         if (cap >= 15) outp[14] = di[4];
     }
+    if (cap >= 25) { outp[23] = h->storage16; outp[24] = h->inited ? h->storage_auto : -1; }
+    if (cap >= 26) outp[25] = h->lev16_builds;
     return VRG_OK;
 }
 

@@ -82,8 +82,17 @@ const char* vrg_last_error(const vrg_handle* h);
  *   "band_capacity"  slots reserved for the narrow band (default: by the volume - one slot per 32 voxels, at least 65536, at most 4 M; the
  *                    arrays grow by themselves when a sweep needs more, so this only saves the re-allocations)
  *   "capacity_floor" smallest capacity of the pool and of the marked-voxel arrays (default 65536; tests lower it)
- *   "storage16"      (takes effect at the next vrg_init) keep intensities as 16-bit level indices (needs <= 16384 distinct values): the dense
- *                    pass streams 2 B instead of 4 B per voxel; results are bit-identical
+ *   "storage16"      (takes effect at the next vrg_init) keep intensities as 16-bit level indices next to the stored volume: the dense pass
+ *                    streams 2 B instead of 4 B (float64 storage: 8 B) per voxel; results are bit-identical.  -1 (default): automatic - when
+ *                    the volume has at most 16384 distinct values, its padded voxels at their stored width (4 B, float64 storage 8 B) take
+ *                    more than "narrow_above" bytes and the index volume can be allocated; otherwise the stored type is streamed, silently
+ *                    (the automatic mode never fails a vrg_init).  The choice reads whole-volume quantities only, so every rank of a slab or
+ *                    replica group chooses alike.  0: never.  1: always - more than 16384 distinct values is then VRG_E_ARG.
+ *                    Costs 2 B per padded voxel of device memory (880x880x640: 1.0 GB, vrg_get_stats out[21]) and one pass over the
+ *                    volume in the first vrg_init after vrg_set_volume; the index volume is kept until the volume is set again, and
+ *                    freed by a vrg_init that does not use it.  ("narrow_alloc_fault" 1 - tests only - makes its allocation fail.)
+ *   "narrow_above"   (takes effect at the next vrg_init) bytes; the size above which storage16 = -1 chooses 16-bit storage (default 300 MiB, where
+ *                    the dense pass stops fitting the Infinity Cache - "nt_loads"; below it the band chain bounds the step; 0: whenever possible)
  *   "sweep_variant"  0 = relabel only the marked voxels (default), 1 = check variant that runs the
  *                    label stencil on every voxel (slow; must give the same state)
  *   "events"         any time; n > 0: time the dense pass of every n-th sweep of a batch with HIP events
@@ -165,7 +174,10 @@ int vrg_get_levels(vrg_handle* h, double* values, int32_t* hist_in, int32_t* his
  * With cap >= 22 also what a large level table costs in device memory: out[20] = bytes of the bin moments (L > 2048 distinct values: up to 4 194 304 bins x 9
  * 64-bit words x 2 classes = 604 MB), out[21] = bytes of the per-voxel level index (4 B per voxel; 2 B with 16-bit storage).
  * With cap >= 23 also out[22] = flips of sweeps with thousands of flips that the compact relabel kernel left to the general one (an excluded voxel
- * within two voxels of the flip), since the handle was created. */
+ * within two voxels of the flip), since the handle was created.
+ * With cap >= 25 also who chose the storage of out[10]: out[23] = option storage16 (-1 automatic, 0 never, 1 always), out[24] = what the automatic mode
+ * decided at the last vrg_init (1: 16-bit storage, 0: the stored type; -1: the option decided, or not initialised).  With cap >= 26 also out[25] = how
+ * often the 16-bit index volume was built since the handle was created (once per volume: a re-init after vrg_set_labels reuses it). */
 int vrg_get_stats(vrg_handle* h, int64_t* out, int64_t cap);
 
 /* Diagnostic builds only (compiled with -DVRG_STAMPS, tools/chain_stamps.py): 64 in-kernel time stamps (100-MHz ticks) of

@@ -52,7 +52,7 @@ for step in "$@"; do
       run refine_like --refine-like
       for nz in 320 80; do run dist1_zslab_880x880x$nz --force-dist --partition zslab --shape 880x880x$nz --no-cpu-baseline --steps 300; done
       for lv in 4095 65535 0; do run 512_levels$lv --no-cpu-baseline --no-side-lines --shape 512x512x170 --steps 100 --levels $lv; done
-      run 880_s16 --storage16 --no-cpu-baseline --no-side-lines
+      run 880_s16 --storage16 --no-cpu-baseline --no-side-lines      # (storage16 = 1; the default line `run 880` chooses 16-bit storage by itself at this size - config.engine.dense_storage says what ran)
       run 1024_s16 --shape 1024x1024x1024 --storage16 --no-cpu-baseline --no-side-lines --steps 200
       for tb in 16 128; do run 880_tubes$tb --tubes $tb --no-cpu-baseline --no-side-lines --steps 100; done ;;
     manyflip) manyflip ;;

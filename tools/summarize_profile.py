@@ -25,7 +25,21 @@ def profiled_shape():
 shape = [int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else profiled_shape()).split('x')]
 planes = int(sys.argv[4]) if len(sys.argv) > 4 else shape[2]
 n_gpus = int(sys.argv[5]) if len(sys.argv) > 5 else 1
-storage16 = bool(int(sys.argv[6])) if len(sys.argv) > 6 else False
+
+
+def profiled_storage16():
+    """Whether the profiled run streamed 16-bit level indices: what its bench line says ran (config.engine.dense_storage) - the
+    default storage is chosen by the volume (option storage16 = -1), so a run without --storage16 may well have."""
+    for log in ('bench_fetch.log', 'bench.json', 'bench_trace.log'):
+        try:
+            line = [l for l in open(os.path.join(src, log)) if l.startswith('{')][-1]
+            return json.loads(line)['config']['engine']['dense_storage'].startswith('u16')
+        except Exception:
+            continue
+    return False
+
+
+storage16 = bool(int(sys.argv[6])) if len(sys.argv) > 6 else profiled_storage16()
 os.makedirs('profiles', exist_ok=True)
 KERNELS = ('k_recount_pipe', 'k_recount_bits', 'k_band', 'k_sweep', 'k_memo', 'k_order', 'k_mark_relabel', 'k_close', 'k_gate')
 
