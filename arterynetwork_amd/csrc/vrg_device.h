@@ -17,9 +17,10 @@
 //   HOST-DRIVEN (be_sweep_once with VRG_SWEEP_SYNC): the host reads the flip count - above 65 536 flips a radix sort ranks them and the chain's
 //           chip-wide kernels do the rest; the full-stencil check variant (and a lowered "small_flips") runs the item functions as device-wide kernels.
 //   stream B, the dense pass (enqueued behind the kernel that raises its request: k_close, or the k_band after a fused sweep):
-//     k_recount_pipe / k_recount_bits : the dense kernel (every listed 1024-voxel unit, HBM-bound, read-only: 4 B intensity of included
-//        voxels + 2 class bits per voxel): region sizes and intensity sums (:113-116, :249-250), reduced by its last workgroup, checked
-//        against the sizes the band side keeps by increments
+//     k_recount_pipe / k_recount_bits : the dense kernel (every listed 1024-voxel unit, HBM-bound, read-only: 4 B intensity - or a 2-B
+//        level index - of included voxels + 2 class bits per voxel): region sizes and intensity sums (:113-116, :249-250), reduced by its
+//        last workgroup, checked against the sizes the band side keeps by increments.  k_recount_pipe (fp32 storage) walks the list two
+//        trips deep; 16-bit storage stays one trip deep in k_recount_bits (two deep measured slower: profiles/depth16_ab_880.json)
 //     -> on several GPUs: slab all-reduce -> k_dense_fin (the same check on the totals, trace sums).
 //   Stream A does not join: it runs up to two sweeps ahead of the dense pass (two copies of the class bits).
 // Labels are updated IN PLACE: measured on MI355X, streaming I + labels read-only runs at 5.8-6.0 TB/s

@@ -191,6 +191,13 @@ __device__ __forceinline__ void stats_bits(SweepAcc& a, uint32_t w, const UnitVa
         }
     }
 }
+// An entry of the unit list as a scalar load: through a pointer into the constant address space, which tells the compiler that
+// nothing in this kernel writes the list (k_gate, the kernel before it on the stream, does) - behind the workgroup barrier that
+// follows the LDS table it would otherwise fetch each entry with a vector load, wait for it alone and broadcast it.
+__device__ __forceinline__ uint32_t ulist_entry(const uint32_t* ulist, uint32_t k) {
+    typedef const uint32_t __attribute__((address_space(4))) cu32;
+    return ((cu32*)ulist)[k];
+}
 template <bool NT>
 __device__ __forceinline__ uint32_t load_cls(const uint32_t* cls, uint32_t u, uint32_t lane) {
     const uint32_t* pc = cls + ((size_t)u << 6) + lane;
@@ -232,6 +239,7 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // SKIP = false (option skip_excluded = 0): the listed units are walked the same way with unpredicated loads - each lane
 // makes the same additions in the same order, a class-0 voxel adding +0.0: bit-identical sums - and the units that are
 // not listed are streamed afterwards for their bytes only.
+// The list entries are read through the scalar cache (ulist_entry).
 template <int UNITS, bool NT, int MODE, bool SKIP>
 __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) {
     VRG_CHAOS_POINT(7);
@@ -242,11 +250,11 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) 
     const uint32_t* __restrict__ ulist = c.ulist;
     const uint32_t n = c.uctl[UC_N];
     const uint32_t last = n ? n - 1u : 0u;
-    uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform: the list is read through the scalar cache)
+    uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform: the list is read through the scalar cache, ulist_entry)
     // (the first trip's units travel with everything else a wave reads first)
     uint32_t uu[UNITS];
 #pragma unroll
-    for (int q = 0; q < UNITS; q++) uu[q] = i < n ? ulist[min(i + q, last)] : 0u;     // (an empty list has no readable entry)
+    for (int q = 0; q < UNITS; q++) uu[q] = i < n ? ulist_entry(ulist, min(i + q, last)) : 0u;     // (an empty list has no readable entry)
     if (MODE == 1) {
         for (uint32_t k = threadIdx.x; k < c.L; k += TPB) s_val[k] = (float)c.lev[k];
         __syncthreads();
@@ -274,7 +282,7 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) 
         const uint32_t in = i + nwaves * UNITS;
         uint32_t un[UNITS], wn[UNITS];
 #pragma unroll
-        for (int q = 0; q < UNITS; q++) { un[q] = __builtin_amdgcn_readfirstlane(ulist[min(in + q, last)]); wn[q] = load_cls<NT>(cls, un[q], lane); }
+        for (int q = 0; q < UNITS; q++) { un[q] = ulist_entry(ulist, min(in + q, last)); wn[q] = load_cls<NT>(cls, un[q], lane); }
 #pragma unroll
         for (int q = 0; q < UNITS; q++) if (in + q >= n) wn[q] = 0u;          // (uniform: slots past the list's end hold nothing)
         UnitVals<MODE> f[UNITS];
@@ -475,11 +483,12 @@ int dense_blocks(const VrgBackend* b, const VrgCtx& c) {
     // 0.0481 with 512; 880x880x80: 0.0466 with 256, 0.0493 with 483, 0.0505 with 512).
     // Streaming pass (skip_excluded = 0): 1 resp. 2 workgroups per CU.
     if (!b->skip) return (int)std::min<uint64_t>(c.lev16 ? 2 * SWEEP_BLOCKS : SWEEP_BLOCKS, std::max<uint64_t>(64, units / 128));
-    // 16-bit storage: six workgroups per CU (one session, 880x880x640 / 1024^3: 1024 -> 0.137 / -, 1280 -> 0.132 / 0.258, 1536 ->
-    // 0.122 / 0.240, 1792 -> 0.122 / -, 2048 -> 0.148 / 0.281 ms)
+    // 16-bit storage: four workgroups per CU.  With the list entries coming through the scalar cache a wave no longer stands still
+    // three times per trip, and fewer waves keep the pass fed (one session, 880x880x640 / 1024^3: 768 -> 0.123 / -, 1024 -> 0.115 / 0.224,
+    // 1280 -> 0.116 / 0.224, 1536 -> 0.126 / 0.245, 1792 -> 0.117 / - ms; with vector loads of the entries 1536 was best: 0.122 / 0.240)
     // (small passes, where the band chain bounds the step: 512x512x170 942 -> 0.0428 ms/step, 384-512 -> 0.0381; 80-plane slab
-    // 1289 -> 0.0516, 512 -> 0.0394; 160 planes 1536 -> 0.0633, 1024 -> 0.0499)
-    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : units <= 200000 ? 4 * SWEEP_BLOCKS : 6 * SWEEP_BLOCKS, std::max<uint64_t>(64, units / 48));
+    // 1289 -> 0.0516, 512 -> 0.0394; 160 planes 1536 -> 0.0633, 1024 -> 0.0499 - measured with vector loads of the entries)
+    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS, std::max<uint64_t>(64, units / 48));
     // fp32: whole or half multiples of the CU count only - 552 or 640 workgroups leave some CUs with a wave more than others for
     // the whole pass (880x880x160: 552 -> 0.058 ms, 384 -> 0.050; 880x880x320: 640 -> 0.103, 512 -> 0.094, 768 -> 0.091 but a
     // slower step, 0.1035 vs 0.1003, the band chain queueing behind three waves per SIMD); one session, tools/gpu_slabsweep.sh
@@ -540,28 +549,40 @@ static void reduce_staged(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void*
 }
 
 
+// The two-trips-deep walk of the listed units (option dense_pipe, default 1): fp32 storage with skip_excluded, k_recount_pipe.
+static bool dense_deep(const VrgBackend* b, const VrgCtx& c) { return b->dense_pipe && b->skip && c.I && !c.lev16; }
+
 // The start / stop events ride on the dispatch itself (hipExtLaunchKernel): no separate event packets in the stream,
 // which cost ~4 us each between two back-to-back recounts.
 template <bool NT, bool SKIP>
-static void launch_recount_as(const VrgCtx& c, int blocks, int check, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+    if constexpr (SKIP) {
+        if (deep) { hipExtLaunchKernelGGL((k_recount_pipe<3, NT>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check); return; }
+    }
     if (c.lev16 && c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(double), st, e_start, e_stop, 0, c, check);
     else if (c.lev16) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check);
     else if (c.I) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 0, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check);
     else hipExtLaunchKernelGGL((k_recount_bits<2, NT, 2, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check);
 }
-// nt: non-temporal loads - for a pass that is larger than the 256-MiB Infinity Cache, where nothing is worth keeping;
-// a smaller slab is read with ordinary loads and then comes out of that cache sweep after sweep.
-static void launch_recount(const VrgCtx& c, int blocks, int check, hipStream_t st, bool skip, bool nt, hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr, int every = 1) {
-    if (check == 1 || check == 2) k_gate<<<1, GATE_THREADS, 0, st>>>(c, every, check);        // waits (on the device) until the sweep's labels are in place; keeps the unit list current
-    if (skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, st, e_start, e_stop); }
-    else { if (nt) launch_recount_as<true, false>(c, blocks, check, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, st, e_start, e_stop); }
+// One dense pass of this handle on stream st: the gate in front of a sweep's pass (checks 1 and 2: it waits, on the device, until the
+// sweep's labels are in place, and keeps the unit list current; also when every pass is counted - with several verifiers this handle
+// counts its share), then the recount.  The passes of the sweeps (checks 1, 2) and a follower's counts of them (4) walk the list two
+// trips deep where there is such a kernel (dense_deep: fp32 storage); the init count (0) and the verify-last count (3) run once: one trip deep.
+// Non-temporal loads (dense_nt): for a pass that is larger than the 256-MiB Infinity Cache, where nothing is worth keeping; a smaller
+// slab is read with ordinary loads and then comes out of that cache sweep after sweep.
+static void launch_recount(VrgBackend* b, const VrgCtx& c, int check, hipStream_t st, hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr) {
+    const int blocks = dense_blocks(b, c);
+    const bool nt = dense_nt(b, c), deep = dense_deep(b, c) && check != 0 && check != 3;
+    if (check == 1 || check == 2) k_gate<<<1, GATE_THREADS, 0, st>>>(c, b->verify_every, check);
+    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, st, e_start, e_stop); }
+    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, st, e_start, e_stop); }
 }
 
 // init: the class bits and the unit list from the labels, then the first count (the sizes the sweeps keep by increments start from it)
 void init_dense(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     k_cls_build<<<2048, TPB, 0, b->sa>>>(c);
     k_ulist_init<<<1, GATE_THREADS, 0, b->sa>>>(c);
-    launch_recount(c, dense_blocks(b, c), 0, b->sa, b->skip != 0, dense_nt(b, c));
+    launch_recount(b, c, 0, b->sa);
     reduce_dense(b, c, cb, user, b->sa);
 }
 
@@ -571,13 +592,7 @@ void init_dense(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
 void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_t e_stop, be_reduce_fn cb, void* user) {
     if (b->serial) HIP_CHECK(hipStreamSynchronize(b->sa));
     const bool ranks = !b->repl && (c.world > 1 || b->comm || cb);
-    if (b->dense_pipe && c.I && !c.lev16 && b->skip) {
-        const int check = ranks ? 1 : 2;
-        k_gate<<<1, GATE_THREADS, 0, b->sb>>>(c, b->verify_every, check);        // (also when every pass is counted: with several verifiers this handle counts its share)
-        if (dense_nt(b, c)) hipExtLaunchKernelGGL((k_recount_pipe<3, true>), dim3(dense_blocks(b, c)), dim3(TPB), 0, b->sb, e_start, e_stop, 0, c, check);
-        else hipExtLaunchKernelGGL((k_recount_pipe<3, false>), dim3(dense_blocks(b, c)), dim3(TPB), 0, b->sb, e_start, e_stop, 0, c, check);
-    } else
-    launch_recount(c, dense_blocks(b, c), ranks ? 1 : 2, b->sb, b->skip != 0, dense_nt(b, c), e_start, e_stop, b->verify_every);
+    launch_recount(b, c, ranks ? 1 : 2, b->sb, e_start, e_stop);
     if (b->serial) HIP_CHECK(hipStreamSynchronize(b->sb));
     // one GPU: the last workgroup of the recount closes the pass itself.  Z-slabs: the slab sums of DENSE_GROUP recounts
     // are summed over the ranks by ONE all-reduce (nothing on the band side waits for it: the decisions use the
@@ -589,7 +604,7 @@ void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_
 // after all and compared with the sizes kept by increments (collective on several ranks)
 void be_verify_last(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     use_device(b);
-    launch_recount(c, dense_blocks(b, c), 3, b->sa, b->skip != 0, dense_nt(b, c));      // (check 3: no gate - launch_recount puts one in front of checks 1 and 2 only)
+    launch_recount(b, c, 3, b->sa);      // (check 3: no gate - launch_recount puts one in front of checks 1 and 2 only)
     reduce_dense(b, c, cb, user, b->sa);
     k_verify_last<<<1, 1, 0, b->sa>>>(c);
     HIP_CHECK(hipStreamSynchronize(b->sa));
@@ -612,18 +627,14 @@ void be_follow_count(VrgBackend* b, const VrgCtx& c, VrgEvents* ev) {
     }
     // the very pass a single GPU runs for this sweep (same kernel, same workgroups, same unit list: the same sums bit for bit); its closing
     // workgroup compares the totals with what the leader filed (check 4)
-    if (b->dense_pipe && c.I && !c.lev16 && b->skip) {
-        if (dense_nt(b, c)) hipExtLaunchKernelGGL((k_recount_pipe<3, true>), dim3(dense_blocks(b, c)), dim3(TPB), 0, b->sa, e0, e1, 0, c, 4);
-        else hipExtLaunchKernelGGL((k_recount_pipe<3, false>), dim3(dense_blocks(b, c)), dim3(TPB), 0, b->sa, e0, e1, 0, c, 4);
-    } else launch_recount(c, dense_blocks(b, c), 4, b->sa, b->skip != 0, dense_nt(b, c), e0, e1);
+    launch_recount(b, c, 4, b->sa, e0, e1);
 }
 
 // what the dense pass of this handle is launched as: {non-temporal loads, storage mode (0 fp32, 1 u16 level index, 2 f64),
 // workgroups, skip_excluded, k_recount_pipe instead of k_recount_bits}
-static bool dense_is_pipe(VrgBackend* b, const VrgCtx& c) { return b->dense_pipe && c.I && !c.lev16 && b->skip; }
 void be_dense_info(VrgBackend* b, const VrgCtx& c, int64_t out[5]) {
     out[0] = dense_nt(b, c) ? 1 : 0; out[1] = c.lev16 ? (c.L <= TAB64_LEVELS ? 3 : 1) : (c.I ? 0 : 2); out[2] = dense_blocks(b, c); out[3] = b->skip ? 1 : 0;
-    out[4] = dense_is_pipe(b, c) ? 1 : 0;
+    out[4] = dense_deep(b, c) ? 1 : 0;
 }
 uint64_t be_dense_bytes(VrgBackend* b, const VrgCtx& c) {
     use_device(b);
