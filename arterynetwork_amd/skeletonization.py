@@ -18,6 +18,10 @@ The centrelines themselves - what the reference reads back from that tool and sa
 are computed here on the GPU: ``skeletonize`` (``vmask_skeleton``: subfield-sequential thinning),
 ``skeletonRadii`` and the file-level ``main``.  They work in the caller's axis order; the axis swap above belongs to
 the external tool's file format and is not applied.
+
+The other two files of that stage (:771-781), ``segmentList.npz`` and ``graphRepresentation.graphml``, come from
+``traceSegments`` (``vmask_segments``: the 26-adjacency graph of the skeleton voxels traced into segments on the GPU by
+pointer jumping), ``saveSegmentList`` and ``writeGraphml``; ``main(..., segments=True)`` writes them.
 """
 from __future__ import annotations
 
@@ -82,6 +86,7 @@ def _skeleton_lib():
     if not getattr(dll.vmask_skeleton, 'argtypes', None):
         p, i64 = C.c_void_p, C.c_int64
         dll.vmask_skeleton.argtypes = [C.c_int, p, i64, i64, i64, p, C.POINTER(i64), C.POINTER(i64)]
+        dll.vmask_segments.argtypes = [C.c_int, p, i64, i64, i64, p, p, i64, p, i64]
     return dll
 
 
@@ -122,9 +127,112 @@ def skeletonRadii(skeleton, vesselVolumeMask, device=0):
     return coords, dt[tuple(coords.T)].astype(np.float64)
 
 
-def main(baseFolder=None):
-    """File-level equivalent of what the reference's skeleton stage leaves behind (:783-790): the skeleton of
-    ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder."""
+SEGMENT_FILE = 'segmentList.npz'
+GRAPH_FILE = 'graphRepresentation.graphml'
+_E_ARG = -1
+
+
+def segmentArrays(skeleton, device=0, info=None):
+    """The segments of the 26-adjacency graph of ``skeleton != 0`` as two arrays: ``offsets``
+    (int64, segments + 1) and ``coords`` (int64, total x 3, the caller's axis order); segment k is
+    ``coords[offsets[k]:offsets[k + 1]]``.  A segment ends at voxels with other than two neighbours and runs through voxels
+    with exactly two; a closed curve of such voxels alone starts and ends at its voxel of smallest raster index.  Open
+    segments run from the end of smaller raster index, closed ones towards the smaller second voxel; segments ascend by
+    (first, second).  A tensor that lives on the GPU gives tensors on the same device.  `info`, when a dict, receives
+    ``segments``, ``nodes``, ``isolated`` and ``rounds`` (pointer-jumping rounds run)."""
+    dll = _skeleton_lib()
+    counts = np.full(5, -1, np.int64)
+    on_device = _G._on_device(skeleton)
+    if on_device:
+        import torch
+        m = _G._u8t(skeleton)
+        dev = _G._dev_index(m)
+        nobj = int(torch.count_nonzero(m))
+        alloc = lambda k: torch.empty(k, dtype=torch.int64, device=m.device)
+        ptr = lambda a: a.data_ptr()
+        torch.cuda.synchronize(m.device)
+    else:
+        m = _G._u8c(skeleton)
+        dev = device
+        nobj = int(np.count_nonzero(m))
+        alloc = lambda k: np.empty(k, np.int64)
+        ptr = lambda a: a.ctypes.data
+    # a curve skeleton has about as many segment entries as voxels: one call; anything denser learns its sizes from the first
+    cap_seg, cap_vox = nobj + 16, 2 * nobj + 16
+    for _ in range(2):
+        offsets, voxels = alloc(cap_seg + 1), alloc(cap_vox)
+        rc = dll.vmask_segments(dev, ptr(m), *m.shape, counts.ctypes.data, ptr(offsets), cap_seg, ptr(voxels), cap_vox)
+        if rc == _E_ARG and counts[0] >= 0 and (counts[0] > cap_seg or counts[1] > cap_vox):
+            cap_seg, cap_vox = int(counts[0]), int(counts[1])
+            continue
+        break
+    _G._check(rc)
+    nseg, total = int(counts[0]), int(counts[1])
+    offsets, voxels = offsets[:nseg + 1], voxels[:total]
+    n1, n2 = int(m.shape[1]), int(m.shape[2])
+    if on_device:
+        import torch
+        rows = torch.div(voxels, n2, rounding_mode='floor')
+        coords = torch.stack((torch.div(rows, n1, rounding_mode='floor'), rows % n1, voxels % n2), dim=1)
+        offsets = offsets.clone()
+    else:
+        coords = np.stack(np.unravel_index(voxels, m.shape), axis=1).astype(np.int64).reshape(total, 3)
+        offsets = offsets.copy()
+    if info is not None:
+        info['segments'], info['nodes'], info['isolated'], info['rounds'] = nseg, int(counts[2]), int(counts[3]), int(counts[4])
+    return offsets, coords
+
+
+def traceSegments(skeleton, device=0, info=None):
+    """The reference's ``segmentList``: a list of segments, each a list of ``(i0, i1, i2)`` tuples of Python ints, in the
+    canonical form and order of `segmentArrays`."""
+    offsets, coords = segmentArrays(skeleton, device=device, info=info)
+    if _G._on_device(offsets):
+        offsets, coords = offsets.cpu().numpy(), coords.cpu().numpy()
+    points = [tuple(c) for c in coords.tolist()]
+    offsets = offsets.tolist()
+    return [points[offsets[k]:offsets[k + 1]] for k in range(len(offsets) - 1)]
+
+
+def saveSegmentList(segmentList, path):
+    """``segmentList.npz`` as the reference's later stages load it (``np.load(path, allow_pickle=True)['segmentList']``):
+    a 1-D object array with one list of tuples per segment."""
+    arr = np.empty(len(segmentList), dtype=object)          # (np.array of a ragged list raises)
+    for k, seg in enumerate(segmentList):
+        arr[k] = [tuple(int(c) for c in p) for p in seg]
+    np.savez_compressed(path, segmentList=arr)
+
+
+def writeGraphml(segmentList, path):
+    """The graph of skeletonization.py:765-769 (``G.add_path(segment, segmentIndex=i)`` for every segment) as GraphML that
+    ``networkx.read_graphml`` parses: the nodes are the voxels, with the id ``str((i0, i1, i2))`` that networkx writes for a
+    tuple node; one edge per consecutive pair of a segment, with the integer attribute ``segmentIndex``."""
+    nodes, edges = {}, {}
+    for k, seg in enumerate(segmentList):
+        ids = [str(tuple(int(c) for c in p)) for p in seg]
+        for a in ids:
+            nodes.setdefault(a, None)
+        for a, b in zip(ids[:-1], ids[1:]):
+            key = (a, b) if (b, a) not in edges else (b, a)   # (an undirected graph keeps one edge per pair: the last index wins)
+            edges[key] = k
+    with open(path, 'w', encoding='utf-8') as f:
+        f.write('<?xml version=\'1.0\' encoding=\'utf-8\'?>\n')
+        f.write('<graphml xmlns="http://graphml.graphdrawing.org/xmlns" xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" '
+                'xsi:schemaLocation="http://graphml.graphdrawing.org/xmlns http://graphml.graphdrawing.org/xmlns/1.0/graphml.xsd">\n')
+        f.write('  <key id="d0" for="edge" attr.name="segmentIndex" attr.type="long" />\n')
+        f.write('  <graph edgedefault="undirected">\n')
+        for a in nodes:
+            f.write('    <node id="{}" />\n'.format(a))
+        for (a, b), k in edges.items():
+            f.write('    <edge source="{}" target="{}">\n      <data key="d0">{}</data>\n    </edge>\n'.format(a, b, k))
+        f.write('  </graph>\n</graphml>\n')
+
+
+def main(baseFolder=None, segments=False):
+    """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
+    ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
+    With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
+    ``(skeleton, segmentList)``."""
     if baseFolder is None:
         baseFolder = os.getcwd()
     vesselVolumeMask, affine = loadVolume(baseFolder, 'vesselVolumeMask.nii.gz')
@@ -132,4 +240,13 @@ def main(baseFolder=None):
     path = os.path.join(baseFolder, SKELETON_FILE)
     saveVolume(skeleton, affine, path, astype=np.uint8)
     print('{} saved to {}.'.format(SKELETON_FILE, path))
-    return skeleton
+    if not segments:
+        return skeleton
+    segmentList = traceSegments(skeleton)
+    path = os.path.join(baseFolder, GRAPH_FILE)
+    writeGraphml(segmentList, path)
+    print('{} saved to {}.'.format(GRAPH_FILE, path))
+    path = os.path.join(baseFolder, SEGMENT_FILE)
+    saveSegmentList(segmentList, path)
+    print('{} saved to {}.'.format(SEGMENT_FILE, path))
+    return skeleton, segmentList
