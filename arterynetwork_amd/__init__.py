@@ -4,5 +4,6 @@ Only what that path needs: csrc/ (HIP kernels + C-ABI, include/vrg.h), the ctype
 mirror of the reference function, synthetic phantoms, and the Z-slab multi-GPU driver.
 """
 from .variationalRegionGrowing import variationalRegionGrowing  # noqa: F401
+from .vesselness import vesselnessFilter, sigmasFromDiameters  # noqa: F401
 
-__all__ = ['variationalRegionGrowing']
+__all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters']

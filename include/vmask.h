@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (SURVEY.md section 8 rows f2-f4): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f7): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -17,6 +17,11 @@
  *                      getSegmentListDetail :565-601), in one canonical orientation and order; DESIGN.md section 9.
  *                      Claimed: exact equality with the sequential model tests/segment_model.py.  Not claimed: agreement
  *                      with the external tool's segments, junction clusters merged into single nodes.
+ *   vmask_vesselness   the multiscale Hessian vesselness filter whose output the pipeline reads as vesselnessFiltered.nii.gz
+ *                      (generateVesselVolume.py:170) and the reference's README.md:61-67 leaves to an external GUI tool:
+ *                      Frangi's measure by the definition below.  Claimed: agreement to 1e-9 with
+ *                      the float64 scipy / numpy model tests/vesselness_model.py outside the measure's one discontinuity.
+ *                      Not claimed: agreement with the external tool's output (its discretisation differs).
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -67,6 +72,29 @@ int vmask_skeleton(int device, const uint8_t* volume, int64_t n0, int64_t n1, in
  * voxels: C-order linear indices; segment k = voxels[offsets[k] .. offsets[k+1]) in the canonical form and order. */
 int vmask_segments(int device, const uint8_t* skeleton, int64_t n0, int64_t n1, int64_t n2,
                    int64_t* counts, int64_t* offsets, int64_t cap_seg, int64_t* voxels, int64_t cap_vox);
+
+/* Frangi vesselness (Frangi et al. 1998) of a 3-D volume I, the maximum over nsig scales; float64 from the taps to the
+ * measure (float32 is an input type only).  Input voxels are assumed finite.
+ *
+ * Taps: for a physical scale sigma and axis a with spacing h_a (spacing == NULL: 1 1 1): s = sigma / h_a, r = int(4 s + 0.5);
+ * on x = -r .. r: phi = exp(-x^2 / 2 s^2) / sum, phi' = -x / s^2 phi, phi'' = (x^2 / s^4 - 1 / s^2) phi.  The operation is
+ * convolution (not correlation) with indices clamped at the volume's faces - scipy.ndimage.gaussian_filter(I, s per axis,
+ * order, mode='nearest', truncate=4.0) in float64.  A radius larger than an extent is legal.
+ * Hessian: H_ab = sigma^2 (d_a d_b G_sigma * I) / (h_a h_b).
+ * Measure: the eigenvalues of H ordered |l1| <= |l2| <= |l3|; V_sigma = 0 unless l2 < 0 and l3 < 0 (bright == 0: l2 > 0 and
+ * l3 > 0), otherwise (1 - exp(-RA^2 / 2 alpha^2)) exp(-RB^2 / 2 beta^2) (1 - exp(-S^2 / 2 gamma^2)) with RA = |l2| / |l3|,
+ * RB = |l1| / sqrt(|l2 l3|), S^2 = l1^2 + l2^2 + l3^2.
+ * gamma > 0 is used for every scale; gamma <= 0 is automatic: per scale half the largest Frobenius norm of H_sigma over the
+ * volume (over the voxels with mask != 0 when a mask is given); a scale whose gamma is 0 contributes 0.
+ * out: float64, max over the scales of V_sigma, 0 where mask == 0.  scale (optional, uint8): index of the first scale that
+ * attains the maximum, 0 where out is 0.  gammas_used (optional, nsig, host): the gamma of every scale.
+ * volume: VRG_F32 or VRG_F64.  VRG_E_ARG: nsig outside 1..32; a sigma or spacing not finite and positive; a radius r < 1 or
+ * r > 64 on any axis; alpha or beta not finite and positive; a shape outside the envelope of the other passes.
+ * VRG_E_MEM: the input, the output and nine float64 volumes do not fit the device (volumes are not processed in slabs);
+ * everything allocated is freed. */
+int vmask_vesselness(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const uint8_t* mask,
+                     const double* sigmas, int nsig, const double* spacing, double alpha, double beta, double gamma, int bright,
+                     double* out, uint8_t* scale, double* gammas_used);
 
 const char* vmask_last_error(void);
 
