@@ -22,6 +22,11 @@ the external tool's file format and is not applied.
 The other two files of that stage (:771-781), ``segmentList.npz`` and ``graphRepresentation.graphml``, come from
 ``traceSegments`` (``vmask_segments``: the 26-adjacency graph of the skeleton voxels traced into segments on the GPU by
 pointer jumping), ``saveSegmentList`` and ``writeGraphml``; ``main(..., segments=True)`` writes them.
+
+``branchTerritories`` (``vmask_territories``: an exact Euclidean feature transform on the GPU) carries the
+segments back to the voxels: every voxel of the mask gets the label of the segment that owns its nearest skeleton voxel, every
+segment its voxel count; ``territoryVolumes`` turns the counts into volumes and ``main(..., segments=True, territories=True)``
+writes ``segmentLabels.nii.gz`` and ``segmentTerritories.npz``.
 """
 from __future__ import annotations
 
@@ -87,6 +92,7 @@ def _skeleton_lib():
         p, i64 = C.c_void_p, C.c_int64
         dll.vmask_skeleton.argtypes = [C.c_int, p, i64, i64, i64, p, C.POINTER(i64), C.POINTER(i64)]
         dll.vmask_segments.argtypes = [C.c_int, p, i64, i64, i64, p, p, i64, p, i64]
+        dll.vmask_territories.argtypes = [C.c_int, p, p, i64, i64, i64, p, i64, p, p, p, p]
     return dll
 
 
@@ -228,11 +234,80 @@ def writeGraphml(segmentList, path):
         f.write('  </graph>\n</graphml>\n')
 
 
-def main(baseFolder=None, segments=False):
+LABEL_FILE = 'segmentLabels.nii.gz'
+TERRITORY_FILE = 'segmentTerritories.npz'
+
+
+def branchTerritories(vesselVolumeMask, skeleton, offsets=None, coords=None, device=0, info=None, return_nearest=False):
+    """The territory map of the segments of `skeleton`: ``labels`` (int32, the mask's shape) and
+    ``sizes`` (int64, segments + 1).  The sites are the voxels with ``skeleton != 0``; a site's label is 1 + the smallest index
+    of a segment it occurs in (a node shared by several segments belongs to the first), 0 for a site in no segment (an
+    isolated voxel).  A voxel with ``vesselVolumeMask != 0`` gets the label of its nearest site by squared Euclidean distance in
+    voxel units, among equidistant sites the one of smallest raster index; 0 outside the mask and where there is no site.
+    ``sizes[l]`` counts the mask voxels with label l (``sizes[0]``: those left unassigned); ``sizes.sum()`` is the mask's voxel
+    count.  `offsets` / `coords` are what `segmentArrays` returns for `skeleton` (computed here when not given).
+    ``return_nearest=True`` adds ``nearest`` (int64: the raster index of the nearest site, -1 outside the mask or without a
+    site).  Tensors that live on the GPU give tensors on the same device.  `info`, when a dict, receives ``segments``."""
+    dll = _skeleton_lib()
+    on_device = _G._on_device(vesselVolumeMask) or _G._on_device(skeleton)
+    if (offsets is None) != (coords is None):
+        raise ValueError('offsets and coords: both or neither')
+    if on_device:
+        import torch
+        ref = vesselVolumeMask if _G._on_device(vesselVolumeMask) else skeleton
+        as_t = lambda a: a if _G._on_device(a) else torch.as_tensor(np.asarray(a), device=ref.device)
+        m, sk = _G._u8t(as_t(vesselVolumeMask)), _G._u8t(as_t(skeleton))
+    else:
+        m, sk = _G._u8c(vesselVolumeMask), _G._u8c(skeleton)
+    if tuple(m.shape) != tuple(sk.shape):
+        raise ValueError('skeleton and vesselVolumeMask must have the same shape')
+    if offsets is None:
+        offsets, coords = segmentArrays(sk, device=device)
+    n1, n2 = int(m.shape[1]), int(m.shape[2])
+    if on_device:
+        dev = _G._dev_index(m)
+        off = as_t(offsets).to(torch.int64).contiguous()
+        co = as_t(coords).to(torch.int64).reshape(-1, 3)
+        vox = ((co[:, 0] * n1 + co[:, 1]) * n2 + co[:, 2]).contiguous()
+        nseg = int(off.numel()) - 1
+        labels = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+        sizes = torch.empty(max(nseg, 0) + 1, dtype=torch.int64, device=m.device)
+        nearest = torch.empty(m.shape, dtype=torch.int64, device=m.device) if return_nearest else None
+        ptr = lambda a: a.data_ptr()
+        torch.cuda.synchronize(m.device)
+    else:
+        dev = device
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        co = np.asarray(coords, dtype=np.int64).reshape(-1, 3)
+        vox = np.ascontiguousarray((co[:, 0] * n1 + co[:, 1]) * n2 + co[:, 2])
+        nseg = int(off.size) - 1
+        labels = np.empty(m.shape, np.int32)
+        sizes = np.empty(max(nseg, 0) + 1, np.int64)
+        nearest = np.empty(m.shape, np.int64) if return_nearest else None
+        ptr = lambda a: a.ctypes.data
+    if nseg < 0 or off.ndim != 1:
+        raise ValueError('offsets must hold segments + 1 entries')
+    _G._check(dll.vmask_territories(dev, ptr(m), ptr(sk), *m.shape, ptr(off), nseg, ptr(vox) if len(vox) else None,
+                                    ptr(labels), ptr(nearest) if return_nearest else None, ptr(sizes)))
+    if info is not None:
+        info['segments'] = nseg
+    return (labels, sizes, nearest) if return_nearest else (labels, sizes)
+
+
+def territoryVolumes(sizes, affine):
+    """Voxel counts as volumes in the affine's units cubed: ``sizes * |det(affine[:3, :3])|``, float64."""
+    return np.asarray(sizes, dtype=np.float64) * abs(float(np.linalg.det(np.asarray(affine, dtype=np.float64)[:3, :3])))
+
+
+def main(baseFolder=None, segments=False, territories=False):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
-    ``(skeleton, segmentList)``."""
+    ``(skeleton, segmentList)``.  With ``territories=True`` as well: ``segmentLabels.nii.gz`` (int32, the mask's affine; label
+    k + 1 is entry k of ``segmentList.npz``, 0 is background or unassigned) and ``segmentTerritories.npz`` (``sizes``: voxels
+    per label, ``volumes``: the same in the affine's units cubed); returns ``(skeleton, segmentList, labels, sizes)``."""
+    if territories and not segments:
+        raise ValueError('territories=True needs segments=True')
     if baseFolder is None:
         baseFolder = os.getcwd()
     vesselVolumeMask, affine = loadVolume(baseFolder, 'vesselVolumeMask.nii.gz')
@@ -242,11 +317,22 @@ def main(baseFolder=None, segments=False):
     print('{} saved to {}.'.format(SKELETON_FILE, path))
     if not segments:
         return skeleton
-    segmentList = traceSegments(skeleton)
+    offsets, coords = segmentArrays(skeleton)
+    points = [tuple(c) for c in coords.tolist()]
+    segmentList = [points[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
     path = os.path.join(baseFolder, GRAPH_FILE)
     writeGraphml(segmentList, path)
     print('{} saved to {}.'.format(GRAPH_FILE, path))
     path = os.path.join(baseFolder, SEGMENT_FILE)
     saveSegmentList(segmentList, path)
     print('{} saved to {}.'.format(SEGMENT_FILE, path))
-    return skeleton, segmentList
+    if not territories:
+        return skeleton, segmentList
+    labels, sizes = branchTerritories(vesselVolumeMask, skeleton, offsets, coords)
+    path = os.path.join(baseFolder, LABEL_FILE)
+    saveVolume(labels, affine, path, astype=np.int32)
+    print('{} saved to {}.'.format(LABEL_FILE, path))
+    path = os.path.join(baseFolder, TERRITORY_FILE)
+    np.savez_compressed(path, sizes=sizes, volumes=territoryVolumes(sizes, affine))
+    print('{} saved to {}.'.format(TERRITORY_FILE, path))
+    return skeleton, segmentList, labels, sizes

@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (DESIGN.md section 9 rows f5-f7): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f8): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -22,6 +22,14 @@
  *                      Frangi's measure by the definition below.  Claimed: agreement to 1e-9 with
  *                      the float64 scipy / numpy model tests/vesselness_model.py outside the measure's one discontinuity.
  *                      Not claimed: agreement with the external tool's output (its discretisation differs).
+ *   vmask_territories  what carries the branches back to the voxels: the reference can give a branch's volume only as a cylinder
+ *                      (fluidSimulation.py:814-842) and keeps a hand-maintained indexVolume of centre voxels
+ *                      (manualCorrectionGUIDetail.py); here every voxel of the mask gets the label of the segment that owns its
+ *                      nearest skeleton voxel and every segment its voxel count: an exact Euclidean feature transform, DESIGN.md
+ *                      section 9, f8.  Claimed: exact equality - labels, nearest, sizes - with the brute-force model
+ *                      tests/territory_model.py, the tie rule below included; bit-identical repeats.  Not claimed: geodesic
+ *                      (inside-the-mask) nearness - where two vessels touch, a voxel can go to the neighbour's centre line -,
+ *                      anisotropic spacing, any per-branch quantity other than the voxel count.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -95,6 +103,27 @@ int vmask_segments(int device, const uint8_t* skeleton, int64_t n0, int64_t n1, 
 int vmask_vesselness(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const uint8_t* mask,
                      const double* sigmas, int nsig, const double* spacing, double alpha, double beta, double gamma, int bright,
                      double* out, uint8_t* scale, double* gammas_used);
+
+/* Branch territories.  mask, skeleton: uint8 volumes; offsets[nseg + 1] and voxels[offsets[nseg]]: what vmask_segments returned
+ * for that skeleton (C-order linear indices; idx below is that index).
+ * Sites: all voxels with skeleton != 0; they need not lie in the mask.
+ * Site label L(s) = 1 + the smallest k such that s occurs in segment k (a node shared by several segments belongs to the one of
+ * smallest index); 0 for a skeleton voxel that occurs in no segment (the isolated voxels, which vmask_segments only counts).
+ * Nearest site N(v) of a voxel with mask != 0: the site of smallest squared Euclidean distance (unit sampling, integers); AMONG
+ * EQUIDISTANT SITES THE ONE OF SMALLEST idx WINS; with no site at all N(v) = -1.
+ * labels (int32): L(N(v)) inside the mask; 0 outside the mask and where N(v) = -1.  Label 0 inside the mask therefore means:
+ * no site, or the nearest site belongs to no segment.
+ * nearest (int64, may be NULL): idx(N(v)); -1 outside the mask or where there is no site.
+ * sizes (int64, nseg + 1): sizes[l] = number of mask voxels with label l (sizes[0]: the in-mask voxels left unassigned); the sum
+ * equals the mask's voxel count.  The output is a pure function of the inputs; repeated runs are bit-identical.
+ * nseg == 0 is legal (offsets and voxels may then be NULL): every label is 0.
+ * VRG_E_ARG: an entry of voxels that is not a skeleton voxel or lies outside the volume, offsets that do not start at 0 or
+ * descend (counted on the device; nothing is written); a shape outside the envelope of the other passes.
+ * VRG_E_MEM: the volume does not fit the device - 20 bytes per voxel of work space beside the two inputs and the outputs (up to
+ * 34 in all with host arrays and nearest); everything allocated is freed. */
+int vmask_territories(int device, const uint8_t* mask, const uint8_t* skeleton, int64_t n0, int64_t n1, int64_t n2,
+                      const int64_t* offsets, int64_t nseg, const int64_t* voxels,
+                      int32_t* labels, int64_t* nearest /* may be NULL */, int64_t* sizes /* nseg + 1 */);
 
 const char* vmask_last_error(void);
 
