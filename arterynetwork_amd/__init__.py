@@ -5,6 +5,8 @@ mirror of the reference function, synthetic phantoms, and the Z-slab multi-GPU d
 """
 from .variationalRegionGrowing import variationalRegionGrowing  # noqa: F401
 from .vesselness import vesselnessFilter, sigmasFromDiameters  # noqa: F401
-from .skeletonization import branchTerritories, territoryVolumes  # noqa: F401
+from .skeletonization import branchTerritories, territoryVolumes, geodesicTerritories  # noqa: F401
+from .geodesic import geodesicDistance  # noqa: F401
 
-__all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'branchTerritories', 'territoryVolumes']
+__all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'branchTerritories', 'territoryVolumes',
+           'geodesicTerritories', 'geodesicDistance']

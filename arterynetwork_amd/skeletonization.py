@@ -27,6 +27,10 @@ pointer jumping, DESIGN.md section 9), ``saveSegmentList`` and ``writeGraphml``;
 segments back to the voxels: every voxel of the mask gets the label of the segment that owns its nearest skeleton voxel, every
 segment its voxel count; ``territoryVolumes`` turns the counts into volumes and ``main(..., segments=True, territories=True)``
 writes ``segmentLabels.nii.gz`` and ``segmentTerritories.npz``.
+
+``geodesicTerritories`` (``vmask_geodesic``: shortest paths inside the mask) is the same map with nearness
+measured through the vessels and in the volume's spacing: a thin vessel beside a thick one no longer takes the thick one's rim.
+``main(..., segments=True, territories=True, geodesic=True)`` writes the two files from it, and ``centrelineDistance.nii.gz``.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ import os
 import numpy as np
 
 from . import generateVesselVolume as _G
+from . import geodesic as _geo
 from .generateVesselVolume import labelVolume, loadVolume, saveVolume
 
 RESULT_DIR = 'skeletonizationResult'
@@ -294,20 +299,84 @@ def branchTerritories(vesselVolumeMask, skeleton, offsets=None, coords=None, dev
     return (labels, sizes, nearest) if return_nearest else (labels, sizes)
 
 
+def geodesicTerritories(vesselVolumeMask, skeleton, offsets=None, coords=None, spacing=None, device=0, info=None, return_distance=False):
+    """The territory map of `branchTerritories` with nearness measured INSIDE the mask ("f9 geodesic"):
+    ``labels`` (int32, the mask's shape) and ``sizes`` (int64, segments + 1).  The seeds are the skeleton voxels that lie in the
+    mask and occur in a segment, with the site labels of `branchTerritories` (1 + the smallest index of a segment the voxel
+    occurs in); skeleton voxels in no segment and skeleton voxels outside the mask are not seeds.  A voxel with
+    ``vesselVolumeMask != 0`` gets the label of the seed at the smallest path length through the 26-adjacency graph of the
+    mask's voxels, a step weighing its Euclidean length in `spacing` (default 1 1 1); where paths of equal length arrive from
+    seeds of different labels the smallest label wins (not the smallest raster index, as in `branchTerritories`).  0 outside the
+    mask and where no seed is reached; ``sizes[0]`` counts the mask voxels left unassigned, ``sizes.sum()`` is the mask's voxel
+    count.  `offsets` / `coords` are what `segmentArrays` returns for `skeleton` (computed here when not given).
+    ``return_distance=True`` adds ``distance`` (float64: the path length to that seed, ``+inf`` where none is reached, -1 outside
+    the mask).  Tensors that live on the GPU give tensors on the same device.  `info`, when a dict, receives ``segments`` and
+    the counts of `geodesic.geodesicDistance`."""
+    on_device = _G._on_device(vesselVolumeMask) or _G._on_device(skeleton)
+    if (offsets is None) != (coords is None):
+        raise ValueError('offsets and coords: both or neither')
+    if on_device:
+        import torch
+        ref = vesselVolumeMask if _G._on_device(vesselVolumeMask) else skeleton
+        as_t = lambda a: a if _G._on_device(a) else torch.as_tensor(np.asarray(a), device=ref.device)
+        m, sk = _G._u8t(as_t(vesselVolumeMask)), _G._u8t(as_t(skeleton))
+    else:
+        m, sk = _G._u8c(vesselVolumeMask), _G._u8c(skeleton)
+    if tuple(m.shape) != tuple(sk.shape):
+        raise ValueError('skeleton and vesselVolumeMask must have the same shape')
+    if offsets is None:
+        offsets, coords = segmentArrays(sk, device=device)
+    n1, n2 = int(m.shape[1]), int(m.shape[2])
+    # every segment entry inside the mask is a seed with the label k + 1 of its segment: the smallest label of a voxel holds
+    if on_device:
+        off = as_t(offsets).to(torch.int64).reshape(-1)
+        co = as_t(coords).to(torch.int64).reshape(-1, 3)
+        nseg = int(off.numel()) - 1
+        if nseg < 0:
+            raise ValueError('offsets must hold segments + 1 entries')
+        vox = (co[:, 0] * n1 + co[:, 1]) * n2 + co[:, 2]
+        lab = torch.repeat_interleave(torch.arange(1, nseg + 1, dtype=torch.int32, device=m.device), off[1:] - off[:-1])
+        keep = m.reshape(-1)[vox] != 0
+        vox, lab = vox[keep].contiguous(), lab[keep].contiguous()
+    else:
+        off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        co = np.asarray(coords, dtype=np.int64).reshape(-1, 3)
+        nseg = int(off.size) - 1
+        if nseg < 0:
+            raise ValueError('offsets must hold segments + 1 entries')
+        vox = (co[:, 0] * n1 + co[:, 1]) * n2 + co[:, 2]
+        lab = np.repeat(np.arange(1, nseg + 1, dtype=np.int32), np.diff(off))
+        keep = m.ravel()[vox] != 0
+        vox, lab = np.ascontiguousarray(vox[keep]), np.ascontiguousarray(lab[keep])
+    distance, labels, sizes = _geo._run(m, vox, lab, max(nseg, 0), spacing, device, return_distance, True, info)
+    if info is not None:
+        info['segments'] = nseg
+    return (labels, sizes, distance) if return_distance else (labels, sizes)
+
+
 def territoryVolumes(sizes, affine):
     """Voxel counts as volumes in the affine's units cubed: ``sizes * |det(affine[:3, :3])|``, float64."""
     return np.asarray(sizes, dtype=np.float64) * abs(float(np.linalg.det(np.asarray(affine, dtype=np.float64)[:3, :3])))
 
 
-def main(baseFolder=None, segments=False, territories=False):
+DISTANCE_FILE = 'centrelineDistance.nii.gz'
+
+
+def main(baseFolder=None, segments=False, territories=False, geodesic=False):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
     ``(skeleton, segmentList)``.  With ``territories=True`` as well: ``segmentLabels.nii.gz`` (int32, the mask's affine; label
     k + 1 is entry k of ``segmentList.npz``, 0 is background or unassigned) and ``segmentTerritories.npz`` (``sizes``: voxels
-    per label, ``volumes``: the same in the affine's units cubed); returns ``(skeleton, segmentList, labels, sizes)``."""
+    per label, ``volumes``: the same in the affine's units cubed); returns ``(skeleton, segmentList, labels, sizes)``.
+    With ``geodesic=True`` as well those two files come from `geodesicTerritories` (nearness inside the mask, the spacing being
+    the norms of the affine's columns) instead of `branchTerritories`, and ``centrelineDistance.nii.gz`` (float32, the mask's
+    affine: the path length to the centre line in the affine's units, ``inf`` where none is reached, -1 outside the mask) is
+    written too; returns ``(skeleton, segmentList, labels, sizes, distance)``."""
     if territories and not segments:
         raise ValueError('territories=True needs segments=True')
+    if geodesic and not territories:
+        raise ValueError('geodesic=True needs territories=True')
     if baseFolder is None:
         baseFolder = os.getcwd()
     vesselVolumeMask, affine = loadVolume(baseFolder, 'vesselVolumeMask.nii.gz')
@@ -328,11 +397,20 @@ def main(baseFolder=None, segments=False, territories=False):
     print('{} saved to {}.'.format(SEGMENT_FILE, path))
     if not territories:
         return skeleton, segmentList
-    labels, sizes = branchTerritories(vesselVolumeMask, skeleton, offsets, coords)
+    if geodesic:
+        spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
+        labels, sizes, distance = geodesicTerritories(vesselVolumeMask, skeleton, offsets, coords, spacing=spacing, return_distance=True)
+    else:
+        labels, sizes = branchTerritories(vesselVolumeMask, skeleton, offsets, coords)
     path = os.path.join(baseFolder, LABEL_FILE)
     saveVolume(labels, affine, path, astype=np.int32)
     print('{} saved to {}.'.format(LABEL_FILE, path))
     path = os.path.join(baseFolder, TERRITORY_FILE)
     np.savez_compressed(path, sizes=sizes, volumes=territoryVolumes(sizes, affine))
     print('{} saved to {}.'.format(TERRITORY_FILE, path))
-    return skeleton, segmentList, labels, sizes
+    if not geodesic:
+        return skeleton, segmentList, labels, sizes
+    path = os.path.join(baseFolder, DISTANCE_FILE)
+    saveVolume(distance, affine, path, astype=np.float32)
+    print('{} saved to {}.'.format(DISTANCE_FILE, path))
+    return skeleton, segmentList, labels, sizes, distance

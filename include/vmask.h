@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (DESIGN.md section 9 rows f5-f8): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f9): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -29,7 +29,16 @@
  *                      section 9, f8.  Claimed: exact equality - labels, nearest, sizes - with the brute-force model
  *                      tests/territory_model.py, the tie rule below included; bit-identical repeats.  Not claimed: geodesic
  *                      (inside-the-mask) nearness - where two vessels touch, a voxel can go to the neighbour's centre line -,
- *                      anisotropic spacing, any per-branch quantity other than the voxel count.
+ *                      anisotropic spacing, any per-branch quantity other than the voxel count (vmask_geodesic supplies the
+ *                      first two).
+ *   vmask_geodesic     path length from chosen voxels through the vessels for every voxel of the mask - the "depth" of
+ *                      partitionCompartmentGUI.py and the "path length" of fluidSimulation.py's terminating-pressure relation,
+ *                      which the reference computes on the centre-line graph only - and the territories by nearness inside the
+ *                      mask, in the volume's spacing: shortest paths in the 26-adjacency graph of the mask's voxels by a
+ *                      block-based label-correcting iteration, DESIGN.md section 9, f9.  Claimed: exact equality - the bits of
+ *                      dist, labels, sizes - with the Dijkstra model tests/geodesic_model.py; bit-identical repeats.  Not
+ *                      claimed: sub-voxel (eikonal) distances, connectivities other than 26, seeds outside the mask, agreement
+ *                      with the reference's graph-level depth.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -124,6 +133,36 @@ int vmask_vesselness(int device, const void* volume, int dtype, int64_t n0, int6
 int vmask_territories(int device, const uint8_t* mask, const uint8_t* skeleton, int64_t n0, int64_t n1, int64_t n2,
                       const int64_t* offsets, int64_t nseg, const int64_t* voxels,
                       int32_t* labels, int64_t* nearest /* may be NULL */, int64_t* sizes /* nseg + 1 */);
+
+/* Geodesic distance and territories inside the mask.  mask: uint8 volume; idx = C-order linear index.
+ * Graph: the vertices are the voxels with mask != 0, the edges join 26-neighbours that are both in the mask, an edge with the
+ * offset delta weighs w(delta) = sqrt((delta0 h0)^2 + (delta1 h1)^2 + (delta2 h2)^2) for spacing = (h0, h1, h2) (NULL: 1 1 1):
+ * a table of 26 values computed once on the host in float64, the squares summed in the order of the axes.
+ * Seeds: seeds[nseed] (int64 idx values, every one a voxel of the mask) and seed_labels[nseed] (int32, 1 .. max_label; NULL: all
+ * 1).  Several entries may name one voxel: THE SMALLEST LABEL HOLDS.  nseed == 0 is legal (seeds may then be NULL).
+ * dist (float64, may be NULL): D(s) = 0 at the seeds; elsewhere in the mask D(v) = min over in-mask neighbours u of
+ * fl(D(u) + w(u - v)), fl the IEEE double addition - the least fixed point, which is what Dijkstra's algorithm computes with the
+ * same addition (fl(a + w) is monotone in a).  +inf at a mask voxel that no seed reaches, -1 outside the mask.
+ * labels (int32, may be NULL): Lab(seed) = its label; for every other voxel with finite D, Lab(v) = min{ Lab(u) : u an in-mask
+ * neighbour with fl(D(u) + w(u - v)) == D(v) } (well founded: w > 0, so D(u) < D(v)).  WHERE PATHS OF EQUAL LENGTH ARRIVE FROM
+ * SEEDS OF DIFFERENT LABELS THE SMALLEST LABEL WINS - not the smallest idx, unlike vmask_territories.  0 outside the mask and
+ * where D = +inf.
+ * sizes (int64, max_label + 1, may be NULL): sizes[l] = number of mask voxels with label l, sizes[0] the unreached ones; the sum
+ * equals the mask's voxel count.
+ * counts (int64, 5, may be NULL): [0] mask voxels, [1] reached voxels (finite D), [2] occupied 8x8x8 bricks, [3] distance
+ * rounds, [4] label rounds (0 when neither labels nor sizes is asked for).
+ * dist, labels, sizes and counts[0..2] are a pure function of the inputs, bit-identical between runs; the round counts describe
+ * the run, not the result.
+ * VRG_E_ARG: a seed outside the volume or on a voxel with mask == 0, a label < 1 or > max_label (counted on the device before
+ * anything is written); a spacing that is not finite and positive, or with max / min > 1000 (the bound keeps fl(D + w) > D for
+ * every D inside the shape envelope); a shape outside the envelope of the other passes.  Nothing is written then.
+ * VRG_E_MEM: the mask, 4 bytes per brick of the volume and 6160 bytes per occupied brick (4112 without labels) do not fit the
+ * device, or the dense outputs where they are host arrays (12 bytes per voxel); everything allocated is freed. */
+int vmask_geodesic(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2,
+                   const int64_t* seeds, const int32_t* seed_labels /* may be NULL */, int64_t nseed,
+                   const double* spacing /* may be NULL */,
+                   double* dist /* may be NULL */, int32_t* labels /* may be NULL */,
+                   int64_t* sizes /* may be NULL */, int64_t max_label, int64_t* counts /* may be NULL */);
 
 const char* vmask_last_error(void);
 
