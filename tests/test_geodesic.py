@@ -144,6 +144,11 @@ CASES['labels-none'] = lambda: (_random((9, 16, 23), 0.6, 77), _corner_and_face_
 CASES['no-seed'] = lambda: (_random((9, 10, 11), 0.5, 78), np.zeros(0, np.int64), None, None)
 
 
+# the spacing ratio at its limit, and spacings that are no representable sums: ties of fl(D + w) decide the labels
+CASES['spacing-1-1000-1'] = functools.partial(_extent_case, (7, 9, 17), 'd60', (1.0, 1000.0, 1.0))
+CASES['spacing-.1-.3-.7'] = functools.partial(_extent_case, (9, 16, 23), 'd60', (0.1, 0.3, 0.7))
+
+
 def _trunk_case():
     mask, _, vox, _ = _trunk_and_thin_vessel()
     return mask, vox, np.repeat(np.asarray([1, 2], np.int32), 40), None
@@ -306,8 +311,10 @@ def test_geodesic_long_dependencies(key):
     dist = _assert_model(key, got, info)[0]
     if key.startswith('line'):
         assert dist.max() == (5999.0 if key.endswith('end') else 3000.0) and info['distance_rounds'] >= 375
+        assert info['label_rounds'] >= 375                              # one label, carried a brick further per round
     else:
         assert info['distance_rounds'] >= (100 if key == 'serpentine-24' else 20)
+        assert info['label_rounds'] >= (100 if key == 'serpentine-24' else 20)
 
 
 @pytest.mark.gpu
@@ -342,7 +349,7 @@ def test_geodesic_ties_and_labels(key):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('key', ['spacing-1-1-2.5', 'spacing-.5-.5-.8'])
+@pytest.mark.parametrize('key', ['spacing-1-1-2.5', 'spacing-.5-.5-.8', 'spacing-1-1000-1', 'spacing-.1-.3-.7'])
 def test_geodesic_spacing(key):
     _assert_model(key)
     mask, seeds, labels, spacing = _model(key)[:4]
@@ -529,3 +536,150 @@ def test_geodesic_main_writes_three_files(tmp_path, capsys):
     d32, aff3 = nifti.loadVolume(str(geo), 'centrelineDistance.nii.gz')
     assert d32.dtype == np.float32 and np.allclose(aff3, aff) and np.array_equal(d32, dist.astype(np.float32))
     assert (d32[m == 0] == -1).all() and (d32[sk != 0] == 0).all()
+
+
+# ------------------------------------------------------------------ the paths that the cases above never enter
+BYTES = np.asarray([1, 2, 0x7f, 0x80, 0xff], np.uint8)
+
+
+def _byte_mask(shape, seed):
+    """A random mask whose non-zero voxels hold 1, 2, 0x7f, 0x80 or 0xff, one aligned 16-byte word of 0x80 only and one of 0x02
+    only, beside words of zeros; the first and the last voxel are set."""
+    rng = np.random.default_rng(seed)
+    m = ((rng.random(shape) < 0.6) * BYTES[rng.integers(0, len(BYTES), shape)]).astype(np.uint8)
+    flat = m.reshape(-1)
+    flat[16:32], flat[32:48], flat[48:64], flat[64:80], flat[80:96] = 0, 0x80, 0, 0x02, 0
+    flat[0], flat[-1] = 0x80, 0x02
+    return m
+
+
+def _abi(dll, mask_ptr, shape, seeds, labels, spacing, max_label):
+    """vmask_geodesic through the C-ABI with host seeds and outputs: (rc, dist, labels, sizes, counts), canaries where nothing is written."""
+    CANARY = -77
+    out = np.full(shape, float(CANARY)), np.full(shape, CANARY, np.int32), np.full(max_label + 1, CANARY, np.int64), np.full(5, CANARY, np.int64)
+    sp = None if spacing is None else np.asarray(spacing, np.float64)
+    rc = dll.vmask_geodesic(0, mask_ptr, *shape, seeds.ctypes.data, labels.ctypes.data, len(seeds), sp.ctypes.data if sp is not None else None,
+                            out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, max_label, out[3].ctypes.data)
+    return (rc,) + out
+
+
+def _bricks(mask):
+    return len({(a // 8, b // 8, c // 8) for a, b, c in np.argwhere(mask).tolist()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape', [(8, 8, 8), (7, 9, 17), (5, 9, 11)])
+def test_geodesic_mask_byte_values(shape):
+    """The mask is "!= 0": bytes such as 0x80, 0x7f and 0x02 count like 1 (the Python wrapper hands on 0 / 1 only, so this goes
+    through the C-ABI)."""
+    mask = _byte_mask(shape, 60)
+    seeds, labels = _corner_and_face_seeds(mask)
+    want = GM.geodesic(mask, seeds, labels, max_label=3)
+    rc, dist, lab, sizes, counts = _abi(G._lib(), mask.ctypes.data, shape, seeds, labels, None, 3)
+    assert rc == 0 and counts[0] == np.count_nonzero(mask) and counts[2] == _bricks(mask)
+    assert dist.tobytes() == want[0].tobytes() and np.array_equal(lab, want[1]) and np.array_equal(sizes, want[2])
+    assert counts[1] == np.isfinite(want[0][mask != 0]).sum()
+
+
+UNALIGNED_SHAPES = [(8, 8, 8), (7, 9, 17), (9, 9, 17)]                   # V % 16 = 0, 15, 1
+
+
+UNALIGNED_SCRIPT = r"""
+import sys
+sys.path.insert(0, {root!r})
+sys.path.insert(0, {tests!r})
+import numpy as np
+import torch                      # before the HIP library: one ROCm runtime per process (INTEGRATION.md)
+from arterynetwork_amd import geodesic as G
+import geodesic_model as GM
+import test_geodesic as T         # the inputs of the test that started this process
+dll = G._lib()
+dev = torch.device('cuda', 0)
+done = 0
+for shape in T.UNALIGNED_SHAPES:
+    V = int(np.prod(shape))
+    mask = T._byte_mask(shape, 61)
+    seeds, labels = T._corner_and_face_seeds(mask)
+    want = GM.geodesic(mask, seeds, labels, max_label=3)
+    for off in (1, 5, 15, 16):
+        buf = torch.full((V + 64,), 0xa5, dtype=torch.uint8, device=dev)      # non-zero bytes in front of and behind the view
+        assert buf.data_ptr() % 16 == 0
+        view = buf[off:off + V]
+        view.copy_(torch.as_tensor(mask.reshape(-1), device=dev))
+        torch.cuda.synchronize(dev)
+        assert view.data_ptr() % 16 == off % 16
+        rc, dist, lab, sizes, counts = T._abi(dll, view.data_ptr(), shape, seeds, labels, None, 3)
+        what = (shape, off)
+        assert rc == 0, (what, dll.vmask_last_error())
+        assert counts[0] == np.count_nonzero(mask) and counts[2] == T._bricks(mask), (what, counts.tolist())
+        assert dist.tobytes() == want[0].tobytes() and np.array_equal(lab, want[1]) and np.array_equal(sizes, want[2]), what
+        back = buf.cpu().numpy()
+        assert (back[:off] == 0xa5).all() and (back[off + V:] == 0xa5).all() and np.array_equal(back[off:off + V], mask.reshape(-1))
+        done += 1
+assert done == 12
+print('UNALIGNED OK')
+"""
+
+
+def test_unaligned_shapes_cover_the_tails():
+    assert [int(np.prod(shape)) % 16 for shape in UNALIGNED_SHAPES] == [0, 15, 1]
+    m = _byte_mask((7, 9, 17), 61).reshape(-1)
+    assert set(np.unique(m).tolist()) == {0, 1, 2, 0x7f, 0x80, 0xff} and (m[32:48] == 0x80).all() and (m[64:80] == 2).all() and m[0] and m[-1]
+
+
+@pytest.mark.gpu
+def test_geodesic_unaligned_device_mask():
+    """A device mask that starts 1, 5, 15 and 16 bytes behind a 16-byte boundary, non-zero bytes in front of it and behind it:
+    k_geo_mark must mask the head of its first aligned word and the tail of its last one (the counts of mask voxels and bricks
+    show a byte too many or too few), and every other kernel reads the mask by the byte.  Own process: torch first."""
+    script = UNALIGNED_SCRIPT.format(root=ROOT, tests=os.path.join(ROOT, 'tests'))
+    out = subprocess.run([sys.executable, '-c', script], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and 'UNALIGNED OK' in out.stdout, out.stdout[-1500:] + out.stderr[-3000:]
+
+
+SEED_SHAPE = (64, 64, 80)                                              # 327 680 voxels: more than the 1024 x 256 threads of k_geo_check / k_geo_seed
+
+
+def _many_seeds():
+    V = int(np.prod(SEED_SHAPE))
+    seeds = np.random.default_rng(70).permutation(V).astype(np.int64)
+    labels = (1 + np.arange(V) % 7).astype(np.int32)
+    return np.concatenate([seeds, seeds[1000:6000]]), np.concatenate([labels, np.ones(5000, np.int32)])      # 5000 duplicates, label 1
+
+
+@pytest.mark.gpu
+def test_geodesic_more_seeds_than_threads():
+    mask = np.ones(SEED_SHAPE, np.uint8)
+    seeds, labels = _many_seeds()
+    assert len(seeds) > 262144 + 5000
+    want = np.full(mask.size, 8, np.int32)
+    np.minimum.at(want, seeds, labels)                                  # of several labels given for one voxel the smallest holds
+    assert (want[seeds[-5000:]] == 1).all() and want.max() == 7
+    info = {}
+    dist, lab, sizes = G.geodesicDistance(mask, seeds, labels, info=info, return_labels=True)
+    assert not dist.any() and dist.dtype == np.float64 and np.array_equal(lab.ravel(), want)
+    assert np.array_equal(sizes, np.bincount(want, minlength=8)) and info['mask_voxels'] == info['reached'] == mask.size and info['bricks'] == 8 * 8 * 10
+    # a bad seed, or a bad label, behind the first trip of the loop: refused, nothing written
+    dll = G._lib()
+    for at, seed, label in ((300000, mask.size, 1), (len(seeds) - 1, -1, 1), (290000, None, 8), (len(seeds) - 1, None, 0)):
+        s, l = seeds.copy(), labels.copy()
+        if seed is not None:
+            s[at] = seed
+        l[at] = label if seed is None else l[at]
+        rc, *out = _abi(dll, mask.ctypes.data, SEED_SHAPE, s, l, None, 7)
+        assert rc == -1 and b'1 seeds' in dll.vmask_last_error() and all((a == -77).all() for a in out)
+
+
+@pytest.mark.gpu
+def test_geodesic_spacing_ratio_limit():
+    """A ratio of exactly 1000 is accepted (and equals the model: 'spacing-1-1000-1' above), the next representable ratios above
+    it are refused with the outputs untouched."""
+    mask, seeds, labels, _ = CASES['spacing-1-1000-1']()
+    dll = G._lib()
+    for spacing in ((1.0, 1000.0000001, 1.0), (1.0, 1.0, float(np.nextafter(1000.0, 2000.0))), (0.001, 1.0, 1.0000000001)):
+        rc, *out = _abi(dll, mask.ctypes.data, mask.shape, seeds, labels, spacing, 3)
+        assert rc == -1 and b'spacing' in dll.vmask_last_error() and all((a == -77).all() for a in out)
+    for spacing in ((1.0, 1000.0, 1.0), (0.5, 500.0, 0.5)):
+        want = GM.geodesic(mask, seeds, labels, spacing, max_label=3)
+        rc, dist, lab, sizes, counts = _abi(dll, mask.ctypes.data, mask.shape, seeds, labels, spacing, 3)
+        assert rc == 0 and dist.tobytes() == want[0].tobytes() and np.array_equal(lab, want[1]) and np.array_equal(sizes, want[2])

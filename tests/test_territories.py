@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import envelope_trace as ET
 import segment_model as SM
 import skeleton_model as M
 import territory_model as TM
@@ -427,3 +428,291 @@ def test_territories_main_writes_labels_and_volumes(tmp_path, capsys):
     off, co = S.segmentArrays(sk)
     want = TM.territories(m, sk, off, _lin(m.shape, co))
     assert np.array_equal(labels, want[0]) and np.array_equal(sizes, want[2])
+
+
+# ------------------------------------------------------------------ the paths that the cases above never enter
+# Every case below is (skeleton, mask); the CPU tests state with tests/envelope_trace.py which branch of k_ter_envelope a case
+# drives, the GPU tests demand exact equality with the model (or with a closed form where the model would be slow).
+def _deep_square(k=0):
+    """160 x 160: the diagonal with sites at (120, k) and (150, 20 + k) - they pop a deep stack below the ring while it is being
+    built (the trace: depth 81, 195 chunk reloads in the build loop for k = 0, but no spill after them) - and, so that a line
+    also spills AGAIN after such a reload, two runs of 50 sites: rows 0-49 in column c0 + 30, rows 50-99 in column c0.  Line c0
+    stacks 50 parabolas of G = 900, the site (50, c0) pops those that start within 30 of it, rows 51-99 push 49 more."""
+    s = np.zeros((160, 160), np.uint8)
+    s[np.arange(160), np.arange(160)] = 1
+    s[120, k] = s[150, 20 + k] = 1
+    c0 = 120 - 8 * k
+    s[0:50, c0 + 30] = 1
+    s[50:100, c0] = 1
+    return s
+
+
+def _narrow_square():
+    """160 x 65: a slanted line of sites and the two runs of _deep_square for column 64, the one active lane of the second
+    64-lane item of an inner extent of 65."""
+    s = np.zeros((160, 65), np.uint8)
+    s[np.arange(160), np.arange(160) * 2 // 5] = 1
+    s[0:50, 34] = 1
+    s[50:160, 64] = 1
+    return s
+
+
+def _sparse_mask(shape, dense, every=97):
+    """The voxels of the slices `dense`, plus every 97th voxel of the volume: the envelope work does not depend on the mask,
+    the brute-force model costs mask voxels x sites."""
+    mask = np.zeros(shape, np.uint8)
+    mask.ravel()[::every] = 1
+    mask[dense] = 1
+    return mask
+
+
+def _deep_case(name):
+    if name == 'deep-1x160x160':
+        sk = _deep_square().reshape(1, 160, 160)
+    elif name == 'deep-160x160x1':
+        sk = _deep_square().reshape(160, 160, 1)
+    elif name == 'deep-3x160x160':
+        sk = np.stack([_deep_square(k) for k in range(3)], axis=0)
+    elif name == 'deep-160x160x3':
+        sk = np.stack([_deep_square(k) for k in range(3)], axis=2)
+    elif name == 'deep-160x3x160':
+        sk = np.stack([_deep_square(k) for k in range(3)], axis=1)
+    elif name == 'deep-1x160x65':
+        sk = _narrow_square().reshape(1, 160, 65)
+    elif name == 'deep-160x65x1':
+        sk = _narrow_square().reshape(160, 65, 1)
+    elif name == 'deep64-1x160x23200':
+        sk = np.zeros((1, 160, 23200), np.uint8)
+        sk[0, :, :160] = _deep_square()
+        return sk, _sparse_mask(sk.shape, np.s_[:, :, :160])
+    elif name == 'deep64-23200x160x1':
+        sk = np.zeros((23200, 160, 1), np.uint8)
+        sk[:160, :, 0] = _deep_square()
+        return sk, _sparse_mask(sk.shape, np.s_[:320])
+    return np.ascontiguousarray(sk), np.ones(sk.shape, np.uint8)
+
+
+# name -> (the envelope pass that must go deep, the lines of it that are traced (None: all), the lines that must EACH meet the
+# conditions (None: the pass as a whole))
+DEEP = {
+    'deep-1x160x160': (1, None, [(0, 120)]),
+    'deep-160x160x1': (0, None, [(0, 120)]),
+    'deep-3x160x160': (1, None, [(0, 120), (1, 112), (2, 104)]),       # (a spill region with o > 0 in every plane)
+    'deep-160x160x3': (0, None, [(0, 120 * 3), (0, 112 * 3 + 1), (0, 104 * 3 + 2)]),
+    'deep-160x3x160': (0, None, [(0, 120), (0, 160 + 112), (0, 320 + 104)]),
+    'deep-1x160x65': (1, None, [(0, 64)]),                             # (lane 0 of the second item; its other 63 lanes are idle)
+    'deep-160x65x1': (0, None, [(0, 64)]),
+    'deep64-1x160x23200': (1, range(160), [(0, 120)]),
+    'deep64-23200x160x1': (0, None, [(0, 120)]),
+}
+
+
+def _trace(name, reload=True):
+    axis, inner, _ = DEEP[name]
+    sk = _deep_case(name)[0]
+    return ET.trace_pass((ET.axis1_lines if axis == 1 else ET.axis0_lines)(sk, inner), reload)
+
+
+def _wide_case(axis, n=23200):
+    """Sparse random sites (density 0.003) in n x 3 x 2 with sites placed at both ends and mid-way on different rows, the long
+    axis moved to `axis`: the winning parabolas carry large, unequal G through the 64-bit arithmetic."""
+    sk = _random((n, 3, 2), 0.003, 300 + axis)
+    sk[0, 0, 0] = sk[n - 1, 2, 1] = sk[n // 2, 1, 0] = sk[n // 2 + 1, 2, 1] = sk[1, 2, 0] = sk[n - 2, 0, 1] = 1
+    order = {0: (0, 1, 2), 1: (1, 0, 2), 2: (2, 1, 0)}[axis]
+    sk = np.ascontiguousarray(sk.transpose(order))
+    return sk, _random(sk.shape, 0.5, 310 + axis)
+
+
+LIMIT_PLANES = [0, 1, 2, 100, 101, 102, 1000, 1002, 5000, 5001, 8191, 8192, 11585, 16384, 21000, 23168, 23169]
+
+
+def _limit_case(axis, n):
+    """23170 x 3 x 2 (n = 23171: one empty plane more), the long axis moved to `axis`.  Sites in neighbouring planes (divisor 2)
+    and thousands of planes apart, in cells of the 3 x 2 cross-section in turn, so that along the long axis the quotients of
+    the start formula run into the thousands with G differences of 0 (exact multiples) and of a few units (just beside an
+    integer), and across it a line of length 3 or 2 meets G differences of up to 23169^2 over a divisor of 2: quotients far
+    above 32768, the entries that are not pushed.  A few random sites on top."""
+    sk = np.zeros((n, 3, 2), np.uint8)
+    for k, p in enumerate(LIMIT_PLANES):
+        sk[p, k % 3, (k // 3) % 2] = 1
+    sk[1000, 2, 1] = sk[21000, 2, 1] = sk[3000, 0, 0] = sk[13000, 0, 0] = 1
+    sk[7000, 1, 0] = sk[7001, 1, 1] = sk[7100, 1, 0] = sk[7101, 1, 0] = 1          # neighbours in one row of the cross-section
+    rng = np.random.default_rng(320)
+    sk[rng.integers(0, 23170, 20), rng.integers(0, 3, 20), rng.integers(0, 2, 20)] = 1
+    order = {0: (0, 1, 2), 1: (1, 0, 2), 2: (2, 1, 0)}[axis]
+    sk = np.ascontiguousarray(sk.transpose(order))
+    return sk, np.ones(sk.shape, np.uint8)
+
+
+NEW = {name: functools.partial(_deep_case, name) for name in DEEP}
+for _axis in range(3):
+    NEW['wide-axis%d' % _axis] = functools.partial(_wide_case, _axis)
+    for _n in (23170, 23171):
+        NEW['limit-%d-axis%d' % (_n, _axis)] = functools.partial(_limit_case, _axis, _n)
+
+
+@functools.lru_cache(maxsize=None)
+def _new_model(name):
+    """(mask, skeleton, offsets, voxels, labels, nearest, sizes) of a case of NEW: the model runs once (read-only)."""
+    sk, mask = NEW[name]()
+    off, vox = _made_up_segments(sk, 7)
+    out = (mask, sk, off, vox) + TM.territories(mask, sk, off, vox)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def test_trace_equals_brute_force_on_random_lines():
+    rng = np.random.default_rng(40)
+    seen = {'ties': 0, 'gaps': 0, 'spilled': 0}
+    for i in range(400):
+        m = int(rng.integers(1, 48))
+        G = rng.integers(-1, (3, 30, 2000)[i % 3], m)                    # few distinct values: equal values and ties abound
+        if i % 7 == 0:
+            G[:] = -1 if i % 2 else 0
+        t = ET.trace_line(G)
+        assert np.array_equal(t.winners, ET.brute_winners(G)), G.tolist()
+        seen['gaps'] += bool((G < 0).any() and (G >= 0).any())
+        seen['ties'] += len(set(G[G >= 0].tolist())) < int((G >= 0).sum())
+        seen['spilled'] += t.spills > 0
+    assert seen['gaps'] > 100 and seen['ties'] > 100 and seen['spilled'] > 5
+    # a line of G = 0 is a stack as deep as the line, spilled and read back; one that pops and grows again
+    t = ET.trace_line([0] * 100)
+    assert (t.depth, t.spills, t.build_reloads, t.read_reloads) == (100, 11, 0, 11) and t.winners.tolist() == list(range(100))
+    G = [900] * 50 + [0] * 50
+    t = ET.trace_line(G)
+    assert t.build_reloads >= 1 and t.spills_after_reload >= 1 and np.array_equal(t.winners, ET.brute_winners(G))
+
+
+def test_existing_diagonals_never_reload_while_building():
+    """Why the deep cases below exist: the 300 x 300 diagonals spill and read back 5100 chunks, but no pop of the build loop
+    ever reaches below the ring."""
+    for lead, lines in ((True, ET.axis1_lines), (False, ET.axis0_lines)):
+        total, _ = ET.trace_pass(lines(_diagonal_case(lead)))
+        assert total.counts() == {'depth': 151, 'spills': 5100, 'build_reloads': 0, 'read_reloads': 5100, 'spills_after_reload': 0}
+    sq = np.zeros((160, 160), np.uint8)                                 # the diagonal and the two popping sites alone
+    sq[np.arange(160), np.arange(160)] = 1
+    sq[120, 0] = sq[150, 20] = 1
+    total, _ = ET.trace_pass(ET.axis1_lines(sq.reshape(1, 160, 160)))
+    assert total.counts() == {'depth': 81, 'spills': 1360, 'build_reloads': 195, 'read_reloads': 1165, 'spills_after_reload': 0}
+
+
+@pytest.mark.parametrize('name', sorted(DEEP))
+def test_deep_cases_reach_their_paths(name):
+    """The conditions of a deep case, per pass and for every line that is named: a stack of at least 2 RING entries, a chunk
+    reload in the build loop, a spill after it, a reload in the read-back loop; the trace's winners are the brute-force ones;
+    and the mutation "load_top without its reload" changes the winners, so a kernel with that defect cannot pass the case."""
+    total, each = _trace(name)
+    for t in [total] + [each[key] for key in DEEP[name][2]]:
+        assert t.depth >= 2 * ET.RING and t.build_reloads >= 1 and t.spills_after_reload >= 1 and t.read_reloads >= 1, t.counts()
+    axis, inner, named = DEEP[name]
+    sk = _deep_case(name)[0]
+    lines = dict((ET.axis1_lines if axis == 1 else ET.axis0_lines)(sk, [c for _, c in named] if axis == 0 or sk.shape[0] == 1 else None))
+    for key in named:
+        want = ET.brute_winners(lines[key])
+        assert np.array_equal(each[key].winners, want)
+        assert not np.array_equal(ET.trace_line(lines[key], reload=False).winners, want)
+
+
+def _kernel_is_32bit(shape):
+    """The kernel's own rule, read from its source: 32-bit arithmetic where n0^2 + n1^2 + n2^2 < 2^bits."""
+    src = open(os.path.join(ROOT, 'arterynetwork_amd', 'csrc', 'vter_device.hip')).read()
+    m = re.search(r'const bool small = \(int64_t\)d\.n0 \* d\.n0 \+ \(int64_t\)d\.n1 \* d\.n1 \+ \(int64_t\)d\.n2 \* d\.n2 < \(\(int64_t\)1 << (\d+)\);', src)
+    assert m, 'the rule that chooses the arithmetic has moved'
+    return sum(int(n) ** 2 for n in shape) < (1 << int(m.group(1)))
+
+
+def test_new_cases_sides_of_the_arithmetic_rule_and_cost():
+    for name in NEW:
+        sk, mask = NEW[name]()
+        assert sk.shape == mask.shape and sk.any()
+        assert np.count_nonzero(mask) * np.count_nonzero(sk) <= 10 ** 8, name         # the model's distance entries
+        small = _kernel_is_32bit(sk.shape)
+        assert small == (not name.startswith(('deep64', 'wide', 'limit-23171'))), name
+    assert _kernel_is_32bit((23170, 3, 2)) and not _kernel_is_32bit((23171, 3, 2)) and not _kernel_is_32bit((23171, 1, 1))
+
+
+def test_limit_cases_hold_the_quotients_they_are_for():
+    """Along the long axis: divisors of 2, exact multiples and near-multiples with quotients in the thousands (below 32768);
+    across it: quotients of 32768 and more (the 32-bit floordiv's "do not push" answer)."""
+    for axis, lines in ((0, ET.axis0_lines), (1, ET.axis1_lines)):
+        div = []
+        ET.trace_pass(lines(_limit_case(axis, 23170)[0]), divisions=div)
+        q = [(a // b, a % b, b) for a, b in div]
+        assert any(b == 2 for _, _, b in q)
+        assert sum(1000 <= f < 32768 and r == 0 for f, r, _ in q) >= 5                # the float quotient may land on either side
+        assert sum(1000 <= f < 32768 and r in (1, 2, b - 1, b - 2) and b > 1000 for f, r, b in q) >= 5
+    for axis, lines in ((1, ET.axis0_lines), (2, ET.axis1_lines)):
+        div = []
+        ET.trace_pass(lines(_limit_case(axis, 23170)[0]), divisions=div)
+        big = [a // b for a, b in div if a // b >= 32768]
+        assert len(big) >= 100 and max(big) > 10 ** 6 and all(b <= 4 for _, b in div)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(NEW))
+def test_territories_untested_paths(name):
+    """Deep stacks with reloads while building and several outer lines; 64-bit arithmetic with content; the 32-bit arithmetic
+    at its last extent and the first extent past it."""
+    mask, sk, off, vox = _new_model(name)[:4]
+    labels, sizes, nearest = _assert_model(mask, sk, off, vox, want=_new_model(name)[4:])
+    if name.startswith('limit-23171'):                                  # the same sites one extent earlier: the same answer
+        axis = int(name[-1])
+        other = _new_model('limit-23170-axis%d' % axis)[5]
+        cut = [slice(None)] * 3
+        cut[axis] = slice(0, 23170)
+        here = np.stack(np.unravel_index(nearest[tuple(cut)].ravel(), sk.shape))
+        there = np.stack(np.unravel_index(other.ravel(), other.shape))
+        assert np.array_equal(here, there)
+
+
+STRIDE_SHAPE = (64, 64, 80)                                            # 327 680 voxels: more than the 1024 x 256 threads of k_ter_sites
+
+
+def _stride_segments(variant):
+    V = int(np.prod(STRIDE_SHAPE))
+    perm = np.random.default_rng(50).permutation(V).astype(np.int64)
+    if variant == 'all':
+        return np.arange(V + 1, dtype=np.int64), perm
+    # the last 70 000 voxels in no segment; the 5 000 earliest segments come again behind entry 262 144 as segments of their own
+    # (the very last entry is segment 0's voxel): the smaller label must hold on the loop's second trip
+    vox = perm[perm < V - 70000]
+    vox = np.concatenate([vox, vox[:5000][::-1]])
+    return np.arange(len(vox) + 1, dtype=np.int64), vox
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('variant', ['all', 'repeats'])
+def test_territories_more_entries_than_threads(variant):
+    ones = np.ones(STRIDE_SHAPE, np.uint8)
+    off, vox = _stride_segments(variant)
+    assert len(vox) > 262144 and len(off) - 1 > 262144
+    L = TM.site_labels(STRIDE_SHAPE, off, vox)
+    if variant == 'repeats':
+        assert L.ravel()[vox[-1]] == 1 and (L.ravel()[-70000:] == 0).all() and L.max() == len(vox) - 5000
+    want = (L, np.arange(ones.size, dtype=np.int64).reshape(STRIDE_SHAPE), np.bincount(L.ravel(), minlength=len(off)).astype(np.int64))
+    labels, sizes, nearest = _assert_model(ones, ones, off, vox, want=want)
+    assert sizes[0] == (0 if variant == 'all' else 70000) and sizes[1:].max() == 1
+
+
+@pytest.mark.gpu
+def test_territories_bad_entry_behind_the_first_trip():
+    dll = S._skeleton_lib()
+    ones = np.ones(STRIDE_SHAPE, np.uint8)
+    off, vox = _stride_segments('all')
+    CANARY = -77
+    for at, bad in ((300000, ones.size), (len(vox) - 1, -1)):
+        v = vox.copy()
+        v[at] = bad
+        labels, nearest, sizes = np.full(STRIDE_SHAPE, CANARY, np.int32), np.full(STRIDE_SHAPE, CANARY, np.int64), np.full(len(off), CANARY, np.int64)
+        rc = dll.vmask_territories(0, ones.ctypes.data, ones.ctypes.data, *STRIDE_SHAPE, off.ctypes.data, len(off) - 1, v.ctypes.data,
+                                   labels.ctypes.data, nearest.ctypes.data, sizes.ctypes.data)
+        assert rc == -1 and b'1 segment entries' in dll.vmask_last_error()
+        assert (labels == CANARY).all() and (nearest == CANARY).all() and (sizes == CANARY).all()
+    o = off.copy()
+    o[290000] = o[290001] + 1                                           # offsets that descend, behind the first trip
+    labels, nearest, sizes = np.full(STRIDE_SHAPE, CANARY, np.int32), np.full(STRIDE_SHAPE, CANARY, np.int64), np.full(len(off), CANARY, np.int64)
+    rc = dll.vmask_territories(0, ones.ctypes.data, ones.ctypes.data, *STRIDE_SHAPE, o.ctypes.data, len(off) - 1, vox.ctypes.data,
+                               labels.ctypes.data, nearest.ctypes.data, sizes.ctypes.data)
+    assert rc == -1 and b'segment entries' in dll.vmask_last_error()
+    assert (labels == CANARY).all() and (nearest == CANARY).all() and (sizes == CANARY).all()
