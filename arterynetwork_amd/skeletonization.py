@@ -31,6 +31,11 @@ writes ``segmentLabels.nii.gz`` and ``segmentTerritories.npz``.
 ``geodesicTerritories`` (``vmask_geodesic``: shortest paths inside the mask) is the same map with nearness
 measured through the vessels and in the volume's spacing: a thin vessel beside a thick one no longer takes the thick one's rim.
 ``main(..., segments=True, territories=True, geodesic=True)`` writes the two files from it, and ``centrelineDistance.nii.gz``.
+
+``branchGraph`` (``vmask_branches``: DESIGN.md section 9, "f10 branch graph") turns the traced skeleton into the graph the later
+stages expect: every cluster of junction voxels is one node, short spurs are pruned by a stated rule, the result is again a thin
+skeleton.  ``branchSegments`` gives its branches as the reference's ``segmentList``; ``main(..., segments=True, prune=(3, 1.0))``
+writes the files from them.
 """
 from __future__ import annotations
 
@@ -98,6 +103,7 @@ def _skeleton_lib():
         dll.vmask_skeleton.argtypes = [C.c_int, p, i64, i64, i64, p, C.POINTER(i64), C.POINTER(i64)]
         dll.vmask_segments.argtypes = [C.c_int, p, i64, i64, i64, p, p, i64, p, i64]
         dll.vmask_territories.argtypes = [C.c_int, p, p, i64, i64, i64, p, i64, p, p, p, p]
+        dll.vmask_branches.argtypes = [C.c_int, p, i64, i64, i64, i64, C.c_double, p, i64, p, p, p, i64, p, p, i64, p, i64]
     return dll
 
 
@@ -239,6 +245,100 @@ def writeGraphml(segmentList, path):
         f.write('  </graph>\n</graphml>\n')
 
 
+BRANCH_FILE = 'branchGraph.npz'
+BRANCH_COUNTS = ('nodes', 'clusters', 'endPoints', 'passThrough', 'branches', 'entries', 'isolated', 'droppedSegments',
+                 'pruneRounds', 'spursRemoved', 'voxelsRemoved', 'labelRounds')
+
+
+class BranchGraph:
+    """What `branchGraph` returns.  ``skeleton`` (uint8 0/1, the input's shape: the skeleton after pruning); per node, ascending
+    by the raster index of its representative voxel: ``nodeCoords`` (int64 N x 3), ``nodeKind`` (0 end point, 1 junction
+    cluster), ``nodeSize`` (voxels of the cluster, 1 for an end point), ``nodeDegree`` (branch ends at the node; a loop counts
+    twice); per branch, in the order of `segmentArrays`: ``branchEnds`` (int64 B x 2 node indices, -1 -1 for a closed curve that
+    touches no node); branch k is ``coords[offsets[k]:offsets[k + 1]]`` and starts and ends at its nodes' representatives;
+    ``counts``: a dict with the keys of `BRANCH_COUNTS`."""
+
+    def __init__(self, skeleton, nodeCoords, nodeKind, nodeSize, nodeDegree, branchEnds, offsets, coords, counts):
+        self.skeleton, self.nodeCoords, self.nodeKind, self.nodeSize, self.nodeDegree = skeleton, nodeCoords, nodeKind, nodeSize, nodeDegree
+        self.branchEnds, self.offsets, self.coords, self.counts = branchEnds, offsets, coords, counts
+
+
+def branchGraph(skeleton, minSpurLength=0, radiusFactor=0.0, vesselVolumeMask=None, dist=None, maxRounds=64, device=0, info=None):
+    """The branch graph of ``skeleton != 0`` ("f10 branch graph") as a `BranchGraph`.  Junction voxels
+    (more than two neighbours) that touch form one node, represented by the member with the most neighbours (then the smallest
+    raster index); an end point is a node too.  The branches are the segments of `segmentArrays` without the two-voxel segments
+    inside a junction cluster, each starting and ending at its nodes' representatives.  A branch from an end point to a junction
+    cluster is a spur when its length L (voxels - 1) is at most `minSpurLength`, or at most `radiusFactor` times `dist` at the
+    cluster's representative; per round every cluster loses at most one spur (the shortest, then the first), the volume is
+    thinned again and the graph rebuilt, until a round finds none or `maxRounds` rounds have run.  `dist` defaults to
+    ``distance_transform_edt(vesselVolumeMask)`` when a mask is given.  With the default parameters nothing is pruned.
+    Host arrays give host arrays, tensors on the GPU give tensors on the same device.  `info`, when a dict, receives the counts."""
+    dll = _skeleton_lib()
+    if dist is None and vesselVolumeMask is not None:
+        dist = _G.distance_transform_edt(vesselVolumeMask, device=device)
+    on_device = _G._on_device(skeleton)
+    counts = np.full(len(BRANCH_COUNTS), -1, np.int64)
+    if on_device:
+        import torch
+        m = _G._u8t(skeleton)
+        dev = _G._dev_index(m)
+        nobj = int(torch.count_nonzero(m))
+        alloc = lambda k, dt=torch.int64: torch.empty(k, dtype=dt, device=m.device)
+        ptr = lambda a: a.data_ptr()
+        if dist is not None:
+            dist = (dist if _G._on_device(dist) else torch.as_tensor(np.asarray(dist), device=m.device)).to(torch.float64).contiguous()
+        out = alloc(tuple(m.shape), torch.uint8)
+        torch.cuda.synchronize(m.device)
+    else:
+        m = _G._u8c(skeleton)
+        dev = device
+        nobj = int(np.count_nonzero(m))
+        alloc = lambda k, dt=np.int64: np.empty(k, dt)
+        ptr = lambda a: a.ctypes.data
+        if dist is not None:
+            dist = np.ascontiguousarray(dist.cpu().numpy() if _G._on_device(dist) else dist, dtype=np.float64)
+        out = alloc(m.shape, np.uint8)
+    if dist is not None and tuple(dist.shape) != tuple(m.shape):
+        raise ValueError('dist and skeleton must have the same shape')
+    # a curve skeleton has fewer nodes and branches than voxels and about as many entries: one call; anything denser learns its sizes from the first
+    cap_node, cap_branch, cap_vox = nobj + 16, nobj + 16, 3 * nobj + 16
+    for _ in range(2):
+        nodes, ends, offsets, voxels = alloc(4 * cap_node), alloc(2 * cap_branch), alloc(cap_branch + 1), alloc(cap_vox)
+        rc = dll.vmask_branches(dev, ptr(m), *m.shape, int(minSpurLength), float(radiusFactor), ptr(dist) if dist is not None else None,
+                                int(maxRounds), ptr(out), counts.ctypes.data, ptr(nodes), cap_node, ptr(ends), ptr(offsets), cap_branch,
+                                ptr(voxels), cap_vox)
+        if rc == _E_ARG and counts[0] >= 0 and (counts[0] > cap_node or counts[4] > cap_branch or counts[5] > cap_vox):
+            cap_node, cap_branch, cap_vox = int(counts[0]), int(counts[4]), int(counts[5])
+            continue
+        break
+    _G._check(rc)
+    nn, nb, total = int(counts[0]), int(counts[4]), int(counts[5])
+    nodes, ends, offsets, voxels = nodes[:4 * nn].reshape(nn, 4), ends[:2 * nb].reshape(nb, 2), offsets[:nb + 1], voxels[:total]
+    n1, n2 = int(m.shape[1]), int(m.shape[2])
+    if on_device:
+        unravel = lambda v: torch.stack((torch.div(torch.div(v, n2, rounding_mode='floor'), n1, rounding_mode='floor'),
+                                         torch.div(v, n2, rounding_mode='floor') % n1, v % n2), dim=1)
+        copy = lambda a: a.clone()
+    else:
+        unravel = lambda v: np.stack(np.unravel_index(v, m.shape), axis=1).astype(np.int64).reshape(len(v), 3)
+        copy = lambda a: a.copy()
+    named = dict(zip(BRANCH_COUNTS, (int(c) for c in counts)))
+    if info is not None:
+        info.update(named)
+    return BranchGraph(out, unravel(nodes[:, 0]), copy(nodes[:, 1]), copy(nodes[:, 2]), copy(nodes[:, 3]), copy(ends), copy(offsets),
+                       unravel(voxels), named)
+
+
+def branchSegments(result):
+    """The branches of a `BranchGraph` as the reference's ``segmentList``: a list of lists of ``(i0, i1, i2)`` tuples of Python ints."""
+    offsets, coords = result.offsets, result.coords
+    if _G._on_device(offsets):
+        offsets, coords = offsets.cpu().numpy(), coords.cpu().numpy()
+    points = [tuple(c) for c in np.asarray(coords).tolist()]
+    offsets = np.asarray(offsets).tolist()
+    return [points[offsets[k]:offsets[k + 1]] for k in range(len(offsets) - 1)]
+
+
 LABEL_FILE = 'segmentLabels.nii.gz'
 TERRITORY_FILE = 'segmentTerritories.npz'
 
@@ -362,7 +462,7 @@ def territoryVolumes(sizes, affine):
 DISTANCE_FILE = 'centrelineDistance.nii.gz'
 
 
-def main(baseFolder=None, segments=False, territories=False, geodesic=False):
+def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -372,7 +472,15 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False):
     With ``geodesic=True`` as well those two files come from `geodesicTerritories` (nearness inside the mask, the spacing being
     the norms of the affine's columns) instead of `branchTerritories`, and ``centrelineDistance.nii.gz`` (float32, the mask's
     affine: the path length to the centre line in the affine's units, ``inf`` where none is reached, -1 outside the mask) is
-    written too; returns ``(skeleton, segmentList, labels, sizes, distance)``."""
+    written too; returns ``(skeleton, segmentList, labels, sizes, distance)``.
+    With ``prune=(minSpurLength, radiusFactor)`` and ``segments=True`` the skeleton goes through `branchGraph` first (`dist` being
+    the distance transform of the mask): ``skeleton.nii.gz`` is the pruned skeleton, ``segmentList.npz`` and
+    ``graphRepresentation.graphml`` hold its branches, ``branchGraph.npz`` the node and branch tables and the counts, and the
+    territories are those of the pruned skeleton's branches.  A voxel of a junction cluster at which no branch ends occurs in no
+    branch: as a site of the territories it has label 0, and the mask voxels nearest to it are counted in ``sizes[0]``.
+    ``prune=None`` writes every file as before."""
+    if prune is not None and not segments:
+        raise ValueError('prune needs segments=True')
     if territories and not segments:
         raise ValueError('territories=True needs segments=True')
     if geodesic and not territories:
@@ -381,12 +489,23 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False):
         baseFolder = os.getcwd()
     vesselVolumeMask, affine = loadVolume(baseFolder, 'vesselVolumeMask.nii.gz')
     skeleton = skeletonize(vesselVolumeMask)
+    if prune is not None:
+        graph = branchGraph(skeleton, minSpurLength=prune[0], radiusFactor=prune[1], vesselVolumeMask=vesselVolumeMask)
+        skeleton = graph.skeleton
     path = os.path.join(baseFolder, SKELETON_FILE)
     saveVolume(skeleton, affine, path, astype=np.uint8)
     print('{} saved to {}.'.format(SKELETON_FILE, path))
     if not segments:
         return skeleton
-    offsets, coords = segmentArrays(skeleton)
+    if prune is not None:
+        offsets, coords = graph.offsets, graph.coords
+        path = os.path.join(baseFolder, BRANCH_FILE)
+        np.savez_compressed(path, nodeCoords=graph.nodeCoords, nodeKind=graph.nodeKind, nodeSize=graph.nodeSize, nodeDegree=graph.nodeDegree,
+                            branchEnds=graph.branchEnds, offsets=offsets, coords=coords,
+                            counts=np.array([graph.counts[k] for k in BRANCH_COUNTS], np.int64), countNames=np.array(BRANCH_COUNTS))
+        print('{} saved to {}.'.format(BRANCH_FILE, path))
+    else:
+        offsets, coords = segmentArrays(skeleton)
     points = [tuple(c) for c in coords.tolist()]
     segmentList = [points[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
     path = os.path.join(baseFolder, GRAPH_FILE)

@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (DESIGN.md section 9 rows f5-f9): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f10): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -16,7 +16,7 @@
  *                      of degree != 2 and run through voxels of degree 2 (the contract of validateSegment :649-680 and
  *                      getSegmentListDetail :565-601), in one canonical orientation and order; DESIGN.md section 9.
  *                      Claimed: exact equality with the sequential model tests/segment_model.py.  Not claimed: agreement
- *                      with the external tool's segments, junction clusters merged into single nodes.
+ *                      with the external tool's segments.  Junction clusters are not merged here: vmask_branches does that.
  *   vmask_vesselness   the multiscale Hessian vesselness filter whose output the pipeline reads as vesselnessFiltered.nii.gz
  *                      (generateVesselVolume.py:170) and the reference's README.md:61-67 leaves to an external GUI tool:
  *                      Frangi's measure by the definition below.  Claimed: agreement to 1e-9 with
@@ -39,6 +39,12 @@
  *                      dist, labels, sizes - with the Dijkstra model tests/geodesic_model.py; bit-identical repeats.  Not
  *                      claimed: sub-voxel (eikonal) distances, connectivities other than 26, seeds outside the mask, agreement
  *                      with the reference's graph-level depth.
+ *   vmask_branches     the "simple branches" that the reference's processSegments / validateSegment expect of segmentList and
+ *                      that it reaches by hand in a GUI: the segments of vmask_segments with every cluster of junction voxels
+ *                      merged into one node, and short spurs pruned by a stated rule; DESIGN.md section 9, f10.  Claimed: exact
+ *                      equality - skeleton, tables, counts - with the sequential model tests/branch_model.py; bit-identical
+ *                      repeats.  Not claimed: pass-through clusters dissolved, agreement with the external tool's segments,
+ *                      spur lengths in physical units, any per-branch quantity.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -163,6 +169,42 @@ int vmask_geodesic(int device, const uint8_t* mask, int64_t n0, int64_t n1, int6
                    const double* spacing /* may be NULL */,
                    double* dist /* may be NULL */, int32_t* labels /* may be NULL */,
                    int64_t* sizes /* may be NULL */, int64_t max_label, int64_t* counts /* may be NULL */);
+
+/* The branch graph.  S = the voxels != 0 of volume (any volume; outside is background); deg, node, path voxel, idx and the
+ * segments of S exactly as vmask_segments defines them.
+ * Junction voxel: deg >= 3.  Cluster: a 26-connected component of junction voxels; its representative is the member of largest
+ * deg, among those the one of smallest idx.
+ * Nodes: the clusters and the end points (deg == 1; its own representative), numbered ascending by idx(representative).
+ * Branches: every segment of S other than the two-voxel segments whose two voxels lie in one cluster, in the segments' order.
+ * A branch's voxels are the segment's, with the node's representative put in front / behind where the end voxel is not the
+ * representative itself (consecutive entries are 26-adjacent except possibly the first and the last pair inside a cluster that
+ * is no clique); its ends are the two node ids, -1 -1 for a closed curve that touches no node; its length L = the segment's
+ * voxel count - 1.  Isolated voxels are only counted.  A cluster with exactly two branch ends stays a node (counted as
+ * pass_through).
+ * Spur: a branch with an end point at one end and a cluster C at the other, and
+ *     L <= min_len || (dist && (double)L <= radius_factor * dist[idx(rep(C))])      (one IEEE multiply, one compare).
+ * A pruning round selects per cluster at most one spur - smallest L, then smallest branch index -, clears every voxel of the
+ * selected segments but the one that belongs to C, thins the volume again (vmask_skeleton, end points kept) and rebuilds the
+ * graph.  Pruning stops at the first round that selects nothing, or after max_rounds rounds.  With min_len == 0 and no dist
+ * nothing is pruned and the thinning never runs.
+ * skeleton (uint8, may be NULL): the volume after pruning, 0/1.  dist (float64 volume, may be NULL): typically vmask_edt(mask).
+ * counts (12): [0] nodes, [1] clusters, [2] end points, [3] pass_through clusters, [4] branches, [5] voxel entries
+ * (= offsets[branches]), [6] isolated voxels, [7] intra-cluster segments dropped, [8] pruning rounds that removed something,
+ * [9] spurs removed, [10] voxels removed by the spur deletions (the thinning's deletions not included), [11] cluster-labelling
+ * rounds of the last graph build (describes the run, not the result).
+ * nodes (cap_node x 4: idx(representative), kind 0 end point / 1 cluster, member count, branch ends incident - a loop counts
+ * twice), branch_ends (cap_branch x 2), offsets (cap_branch + 1), voxels (cap_vox): all four NULL = counts (and skeleton) only;
+ * too small a capacity: VRG_E_ARG with the needed sizes in counts, nothing else written.
+ * Everything but counts[11] is a pure function of the inputs, bit-identical between runs.
+ * VRG_E_ARG: min_len, max_rounds or radius_factor negative, radius_factor not finite; a shape outside the envelope of the
+ * other passes.  VRG_E_MEM: device memory does not fit - the volume, dist where it is a host array, up to 80 bytes per object
+ * voxel, 44 per segment, 8 per segment entry, and what vmask_segments and vmask_skeleton take while they run; everything
+ * allocated is freed. */
+int vmask_branches(int device, const uint8_t* volume, int64_t n0, int64_t n1, int64_t n2,
+                   int64_t min_len, double radius_factor, const double* dist /* may be NULL */, int64_t max_rounds,
+                   uint8_t* skeleton /* may be NULL */, int64_t* counts,
+                   int64_t* nodes, int64_t cap_node, int64_t* branch_ends, int64_t* offsets, int64_t cap_branch,
+                   int64_t* voxels, int64_t cap_vox);
 
 const char* vmask_last_error(void);
 
