@@ -6,7 +6,8 @@ mirror of the reference function, synthetic phantoms, and the Z-slab multi-GPU d
 from .variationalRegionGrowing import variationalRegionGrowing  # noqa: F401
 from .vesselness import vesselnessFilter, sigmasFromDiameters  # noqa: F401
 from .skeletonization import branchTerritories, territoryVolumes, geodesicTerritories  # noqa: F401
+from .skeletonization import branchMorphometry, BranchMorphometry, deriveMorphometry, pathLengths, writeMorphometry  # noqa: F401
 from .geodesic import geodesicDistance  # noqa: F401
 
 __all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'branchTerritories', 'territoryVolumes',
-           'geodesicTerritories', 'geodesicDistance']
+           'geodesicTerritories', 'geodesicDistance', 'branchMorphometry', 'BranchMorphometry', 'deriveMorphometry', 'pathLengths', 'writeMorphometry']

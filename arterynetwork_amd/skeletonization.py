@@ -36,6 +36,12 @@ measured through the vessels and in the volume's spacing: a thin vessel beside a
 stages expect: every cluster of junction voxels is one node, short spurs are pruned by a stated rule, the result is again a thin
 skeleton.  ``branchSegments`` gives its branches as the reference's ``segmentList``; ``main(..., segments=True, prune=(3, 1.0))``
 writes the files from them.
+
+``branchMorphometry`` (``vmask_morphometry``: DESIGN.md section 9, "f11 branch morphometry") measures that graph: per branch the
+path length, the chord, the tortuosity and the radius statistics, per node the radius, per three-branch bifurcation the angles and
+the radius laws, and from roots the path distance and depth of every node.  ``main(..., segments=True, prune=(3, 1.0),
+morphometry=True)`` writes ``branchMorphometry.npz``, ``graphRepresentationWithEdgeInfo.graphml``, ``segmentInfoDict.pkl`` and
+``nodeInfoDict.pkl`` from it.
 """
 from __future__ import annotations
 
@@ -104,6 +110,7 @@ def _skeleton_lib():
         dll.vmask_segments.argtypes = [C.c_int, p, i64, i64, i64, p, p, i64, p, i64]
         dll.vmask_territories.argtypes = [C.c_int, p, p, i64, i64, i64, p, i64, p, p, p, p]
         dll.vmask_branches.argtypes = [C.c_int, p, i64, i64, i64, i64, C.c_double, p, i64, p, p, p, i64, p, p, i64, p, i64]
+        dll.vmask_morphometry.argtypes = [C.c_int, i64, i64, i64, p, p, i64, p, p, p, i64, p, p, i64, i64, p, p, p, p, p, p, p, p, p]
     return dll
 
 
@@ -339,6 +346,362 @@ def branchSegments(result):
     return [points[offsets[k]:offsets[k + 1]] for k in range(len(offsets) - 1)]
 
 
+MORPHOMETRY_FILE = 'branchMorphometry.npz'
+EDGE_INFO_GRAPH_FILE = 'graphRepresentationWithEdgeInfo.graphml'
+SEGMENT_INFO_FILE = 'segmentInfoDict.pkl'
+NODE_INFO_FILE = 'nodeInfoDict.pkl'
+# the columns of vmask_morphometry's two per-branch tables (include/vmask.h)
+_MOR_INT, _MOR_F64 = 24, 5
+MORPHOMETRY_RAW = ('stepCounts', 'jumps', 'jumpOffset', 'radiusCount', 'radiusSum', 'radiusDevSq', 'radiusMin', 'radiusMax', 'endDir', 'chord',
+                   'pathLength', 'nodeRadius', 'incidentBranch', 'incidentEnd', 'entryRadius')
+MORPHOMETRY_DEPTH = ('pathDistance', 'parentBranch', 'depthLevel', 'depthVoxel', 'branchLevel')
+MORPHOMETRY_BRANCH = ('eculideanLength', 'tortuosity', 'voxelLength', 'meanRadius', 'sigma', 'aspectRatio', 'type', 'localBifurcationTorque')
+MORPHOMETRY_BIFURCATION = ('bifurcationNode', 'bifurcationBranches', 'localBifurcationAmplitude', 'remoteBifurcationAmplitude', 'localBifurcationTilt',
+                           'remoteBifurcationTilt', 'cubicLawResult', 'squareLawResult', 'minRadiusRatio', 'maxRadiusRatio', 'lengthRatio', 'normalVector')
+
+
+class BranchMorphometry:
+    """What `branchMorphometry` returns: one attribute per name of `MORPHOMETRY_RAW`, `MORPHOMETRY_BRANCH`, `MORPHOMETRY_BIFURCATION`
+    and - ``None`` without roots - `MORPHOMETRY_DEPTH`; ``spacing`` (float64, 3), ``localSteps``, ``roots`` (int64 node indices) and
+    ``depthRounds``.  ``names()`` lists the arrays that are set."""
+
+    def names(self):
+        return [k for k in MORPHOMETRY_RAW + MORPHOMETRY_DEPTH + MORPHOMETRY_BRANCH + MORPHOMETRY_BIFURCATION if getattr(self, k, None) is not None]
+
+
+def stepWeights(spacing):
+    """The length of a step of every class c = 4 |d0| + 2 |d1| + |d2| - 1: the square root of the squared spacings of the set axes,
+    summed in the order of the axes (float64, 7)."""
+    h = np.asarray(spacing, np.float64)
+    bits = np.array([[(c + 1) >> 2 & 1, (c + 1) >> 1 & 1, (c + 1) & 1] for c in range(7)], np.float64)
+    return _norm3(bits * h)
+
+
+def _norm3(v):
+    """sqrt((v0^2 + v1^2) + v2^2) along the last axis: one stated order (np.linalg.norm leaves it open)."""
+    v = np.asarray(v, np.float64)
+    return np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+
+
+def pathLengths(stepCounts, jumpOffset, spacing):
+    """``pathLength`` from the integer outputs: ((0 + stepCounts[0] w_0) + .. + stepCounts[6] w_6) + |front jump| + |back jump| with
+    the weights of `stepWeights` and a jump's length being `_norm3` of its offset times the spacing - each product and sum one
+    IEEE double operation, in this order.  The library does the same on the host; the two agree to the bit."""
+    h = np.asarray(spacing, np.float64)
+    w = stepWeights(h)
+    sc = np.asarray(stepCounts, np.int64).reshape(-1, 7)
+    jo = np.asarray(jumpOffset, np.int64).reshape(-1, 2, 3)
+    out = np.zeros(len(sc), np.float64)
+    for c in range(7):
+        out = out + sc[:, c].astype(np.float64) * w[c]
+    out = out + _norm3(jo[:, 0].astype(np.float64) * h)
+    return out + _norm3(jo[:, 1].astype(np.float64) * h)
+
+
+def _angle(a, b):
+    """The angle between the rows of a and b in degrees, from the clipped cosine."""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        c = (a * b).sum(axis=-1) / (_norm3(a) * _norm3(b))
+    return np.arccos(np.clip(c, -1.0, 1.0)) / np.pi * 180
+
+
+def deriveMorphometry(raw, offsets, branchEnds, nodeKind, spacing):
+    """The quantities that follow from vmask_morphometry's outputs by B- or N-sized numpy work; `raw` maps the names of
+    `MORPHOMETRY_RAW` (and of `MORPHOMETRY_DEPTH`, or None) to host arrays.  Returns a dict with the names of `MORPHOMETRY_BRANCH` and
+    `MORPHOMETRY_BIFURCATION`; the formulas are those of `branchMorphometry`'s docstring."""
+    h = np.asarray(spacing, np.float64)
+    off = np.asarray(offsets, np.int64)
+    ends = np.asarray(branchEnds, np.int64).reshape(-1, 2)
+    kind = np.asarray(nodeKind, np.int64)
+    B = len(off) - 1
+    n = np.diff(off)
+    out = {}
+    with np.errstate(invalid='ignore', divide='ignore'):
+        out['eculideanLength'] = _norm3(raw['chord'].astype(np.float64) * h)
+        out['tortuosity'] = raw['pathLength'] / out['eculideanLength']
+        out['voxelLength'] = n.astype(np.int64)
+        out['meanRadius'] = raw['radiusSum'] / raw['radiusCount'].astype(np.float64)
+        out['sigma'] = np.sqrt(raw['radiusDevSq'] / raw['radiusCount'].astype(np.float64))
+        out['aspectRatio'] = raw['pathLength'] / out['meanRadius']
+    open_ = ends[:, 0] >= 0 if B else np.zeros(0, bool)
+    terminating = np.zeros(B, bool)
+    terminating[open_] = (kind[ends[open_, 0]] == 0) | (kind[ends[open_, 1]] == 0)
+    out['type'] = np.where(open_, np.where(terminating, 0, 1), -1).astype(np.int64)
+    # ---- the bifurcation table
+    ib, ie = np.asarray(raw['incidentBranch'], np.int64).reshape(-1, 3), np.asarray(raw['incidentEnd'], np.int64).reshape(-1, 3)
+    rows = np.flatnonzero((ib[:, 0] >= 0) & (n[np.maximum(ib, 0)] >= 3).all(axis=1)) if len(ib) and B else np.zeros(0, np.int64)
+    K = len(rows)
+    b3, e3 = ib[rows], ie[rows]                                           # K x 3, ascending branch index
+    local = raw['endDir'].reshape(-1, 2, 3)[b3, e3].astype(np.float64) * h             # K x 3 x 3: from the node inwards
+    remote = (raw['chord'][b3] * np.where(e3 == 0, 1, -1)[..., None]).astype(np.float64) * h   # from the node to the far end
+    with np.errstate(invalid='ignore', divide='ignore'):
+        unit = local / _norm3(local)[..., None]
+    cos = np.stack([(unit[:, 0] * unit[:, 1]).sum(-1), (unit[:, 1] * unit[:, 2]).sum(-1), (unit[:, 2] * unit[:, 0]).sum(-1)], axis=1).reshape(K, 3)
+    order = np.array([[0, 1, 2], [1, 2, 0], [2, 0, 1]])[np.argmax(cos, axis=1) if K else np.zeros(0, np.int64)].reshape(K, 3)
+    if raw.get('parentBranch') is not None and K:
+        pb = np.asarray(raw['parentBranch'], np.int64)[rows]
+        is_parent = b3 == pb[:, None]
+        known = is_parent.any(axis=1)
+        by_depth = np.argsort(is_parent, axis=1, kind='stable')          # the two children in ascending order, the parent last
+        order = np.where(known[:, None], by_depth, order)
+    take = lambda a: np.take_along_axis(a, order[..., None] if a.ndim == 3 else order, axis=1)
+    b3, local, remote = take(b3), take(local), take(remote)
+    out['bifurcationNode'], out['bifurcationBranches'] = rows.astype(np.int64), b3.reshape(K, 3)
+    out['localBifurcationAmplitude'] = _angle(local[:, 0], local[:, 1])
+    out['remoteBifurcationAmplitude'] = _angle(remote[:, 0], remote[:, 1])
+    against = -local[:, 2]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for name, v in (('localBifurcationTilt', local), ('remoteBifurcationTilt', remote)):
+            half = v[:, 0] / _norm3(v[:, 0])[:, None] + v[:, 1] / _norm3(v[:, 1])[:, None]
+            out[name] = np.where(_norm3(half) > 1e-4, _angle(half, against), np.nan)
+        r, l = out['meanRadius'][b3].reshape(K, 3), raw['pathLength'][b3].reshape(K, 3)
+        out['cubicLawResult'] = (r[:, 0] ** 3 + r[:, 1] ** 3) / r[:, 2] ** 3
+        out['squareLawResult'] = (r[:, 0] ** 2 + r[:, 1] ** 2) / r[:, 2] ** 2
+        out['minRadiusRatio'] = np.minimum(r[:, 0], r[:, 1]) / r[:, 2]
+        out['maxRadiusRatio'] = np.maximum(r[:, 0], r[:, 1]) / r[:, 2]
+        out['lengthRatio'] = np.minimum(l[:, 0], l[:, 1]) / l[:, 2]
+        normal = np.cross(local[:, 0], local[:, 1]).reshape(K, 3)
+        out['normalVector'] = normal / _norm3(normal)[:, None]
+    # ---- per branch between two tabulated bifurcations: the angle of their normals, folded to at most 90 degrees
+    row_of = np.full(max(len(kind), 1), -1, np.int64)                     # (a closed curve alone: no node to look up)
+    row_of[rows] = np.arange(K)
+    torque = np.full(B, np.nan)
+    both = np.flatnonzero(open_ & (row_of[np.maximum(ends[:, 0], 0)] >= 0) & (row_of[np.maximum(ends[:, 1], 0)] >= 0)) if B else np.zeros(0, np.int64)
+    if len(both):
+        t = _angle(out['normalVector'][row_of[ends[both, 0]]], out['normalVector'][row_of[ends[both, 1]]])
+        torque[both] = np.where(t > 90, 180 - t, t)
+    out['localBifurcationTorque'] = torque
+    return out
+
+
+def _root_indices(roots, nodeCoords):
+    """Node indices from `roots`: an item that is a sequence of three numbers is a coordinate and must be a node's representative."""
+    if roots is None:
+        return np.zeros(0, np.int64)
+    nc = np.asarray(nodeCoords.cpu() if _G._on_device(nodeCoords) else nodeCoords, np.int64).reshape(-1, 3)
+    items = roots.tolist() if hasattr(roots, 'tolist') else roots
+    items = list(items) if isinstance(items, (list, tuple)) else [items]
+    out = []
+    for r in items:
+        if np.ndim(r) == 0:
+            k = int(r)
+            if not 0 <= k < len(nc):
+                raise ValueError('root {} is no node index (the graph has {} nodes)'.format(k, len(nc)))
+        else:
+            if len(r) != 3:
+                raise ValueError('a root is a node index or a coordinate triple')
+            hit = np.flatnonzero((nc == np.asarray(r, np.int64)).all(axis=1))
+            if not len(hit):
+                raise ValueError('root {} is no node representative'.format(tuple(int(c) for c in r)))
+            k = int(hit[0])
+        out.append(k)
+    return np.array(out, np.int64)
+
+
+def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roots=None, localSteps=5, device=0, info=None):
+    """The morphometry of a `BranchGraph` (``vmask_morphometry``, DESIGN.md section 9, "f11 branch morphometry") as a
+    `BranchMorphometry`.  `dist` is the radius volume (default ``distance_transform_edt(vesselVolumeMask)``), `spacing` the voxel
+    size per axis (default 1 1 1; positive, finite, max / min <= 1000), `roots` node indices or coordinate triples of node
+    representatives (``ValueError`` when a triple is none), `localSteps` the reach of the local direction.  A host graph gives
+    host arrays, a graph of tensors on the GPU gives tensors on the same device (the derived quantities are computed from host
+    copies of the B- and N-sized outputs and sent back).  `info`, when a dict, receives ``depthRounds`` and ``levelRounds``.
+
+    From the kernels, for a branch b of n entries (include/vmask.h has the summation order):
+      stepCounts[b, c]   consecutive entry pairs of class c = 4 |d0| + 2 |d1| + |d2| - 1;  jumps[b]: pairs that are not 26-adjacent
+      jumpOffset[b]      the offset of the first / the last pair where it is a jump (inside a cluster that is no clique), else 0
+      radiusCount, radiusSum, radiusDevSq, radiusMin, radiusMax
+                         of dist at the interior entries 1 .. n - 2 (both entries when n == 2); radiusDevSq = sum (r - mean)^2
+      endDir[b, e]       the offset from the end entry e (0 first, 1 last) to the entry min(localSteps, n - 1) positions inwards
+      chord[b]           last entry - first entry
+      pathLength[b]      `pathLengths`: sum over the classes 0 .. 6 of stepCounts w_c, plus the two jump lengths
+      entryRadius        dist at every entry of ``graph.coords``
+      nodeRadius         dist at the representative;  incidentBranch / incidentEnd[v]: the three branches that end at a node with
+                         exactly three ends of three distinct branches, ascending, and which end (0 first, 1 last); else -1
+      pathDistance       with roots: D(root) = 0, D(v) = min over branches b between u != v of fl(D(u) + pathLength[b]); inf unreached
+      parentBranch       the smallest b with fl(D(u) + pathLength[b]) == D(v), D(u) < D(v); -1 at roots and unreached nodes
+      depthLevel, depthVoxel   0 at the roots, + 1 / + (n_b - 1) along parentBranch, -1 unreached; branchLevel[b]: the larger
+                         depthLevel of its ends, -1 where either is unreached
+    Derived here (`deriveMorphometry`):
+      eculideanLength = |chord * spacing| (sic, the reference's spelling); tortuosity = pathLength / eculideanLength (inf for a closed
+      branch); voxelLength = n; meanRadius = radiusSum / radiusCount; sigma = sqrt(radiusDevSq / radiusCount) (np.std's population
+      form); aspectRatio = pathLength / meanRadius; type: 0 terminating (an end is an end point), 1 bifurcating, -1 a closed curve
+      without a node (graphRelated.py:81-84).
+    The bifurcation table covers the nodes with incident branches whose three branches have n >= 3 (bifurcationNode: node index;
+    bifurcationBranches: child, child, parent).  The parent is the node's parentBranch when that is one of the three, the children
+    then ascend by branch index; otherwise, with the unit local directions u0, u1, u2 in ascending branch index, the first maximum
+    of u0.u1, u1.u2, u2.u0 names the children - orders [0, 1, 2], [1, 2, 0], [2, 0, 1], the third being the parent
+    (graphRelated.py:190-207).  THE LOCAL DIRECTION IS THE CHORD endDir * spacing OVER localSteps VOXELS, NOT THE REFERENCE'S
+    WEIGHTED SPLINE DERIVATIVE; the remote direction runs from the node's representative to the far end of the branch.
+    local / remoteBifurcationAmplitude: the angle between the children's directions, degrees, from the clipped cosine;
+    local / remoteBifurcationTilt: the angle between the children's half-angle vector (sum of the unit directions) and minus the
+    parent's local direction, NaN when that vector's norm is <= 1e-4; cubicLawResult = (r1^3 + r2^3) / r3^3, squareLawResult
+    likewise, min / maxRadiusRatio = min / max(r1, r2) / r3, lengthRatio = min(l1, l2) / l3 with the branches' meanRadius and
+    pathLength; normalVector = the unit cross product of the children's local directions.  localBifurcationTorque (per branch
+    whose two ends are both in the table, else NaN): the angle between the two normals, folded to at most 90 degrees."""
+    if int(localSteps) < 1:
+        raise ValueError('localSteps must be at least 1')
+    on_device = _G._on_device(graph.offsets)
+    shape = tuple(int(k) for k in graph.skeleton.shape)
+    if dist is None:
+        if vesselVolumeMask is None:
+            raise ValueError('dist or vesselVolumeMask is needed')
+        dist = _G.distance_transform_edt(vesselVolumeMask, device=device)
+    if tuple(dist.shape) != shape:
+        raise ValueError('dist and the graph\'s skeleton must have the same shape')
+    h = np.ones(3, np.float64) if spacing is None else np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))
+    root_ix = _root_indices(roots, graph.nodeCoords)
+    n1, n2 = shape[1], shape[2]
+    B, N, R = int(graph.offsets.shape[0]) - 1, int(graph.nodeCoords.shape[0]), len(root_ix)
+    if on_device:
+        import torch
+        tdev = graph.offsets.device
+        dev = _G._dev_index(graph.offsets)
+        dist = (dist if _G._on_device(dist) else torch.as_tensor(np.asarray(dist), device=tdev)).to(torch.float64).contiguous()
+        lin = lambda c: ((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2]).to(torch.int64).contiguous()
+        off, ends = graph.offsets.to(torch.int64).contiguous(), graph.branchEnds.to(torch.int64).contiguous()
+        rt = torch.as_tensor(root_ix, device=tdev)
+        alloc = lambda shp, dt: torch.empty(shp, dtype=torch.int64 if dt is np.int64 else torch.float64, device=tdev)
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        host = lambda a: a.cpu().numpy()
+        torch.cuda.synchronize(tdev)
+    else:
+        dev = device
+        dist = np.ascontiguousarray(dist.cpu().numpy() if _G._on_device(dist) else dist, dtype=np.float64)
+        lin = lambda c: np.ascontiguousarray((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2], dtype=np.int64)
+        off, ends = np.ascontiguousarray(graph.offsets, dtype=np.int64), np.ascontiguousarray(graph.branchEnds, dtype=np.int64)
+        rt = root_ix
+        alloc = lambda shp, dt: np.empty(shp, dt)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        host = lambda a: a
+    vox, nodevox = lin(graph.coords.reshape(-1, 3)), lin(graph.nodeCoords.reshape(-1, 3))
+    bi, bf = alloc((B, _MOR_INT), np.int64), alloc((B, _MOR_F64), np.float64)
+    radius, incident = alloc((N,), np.float64), alloc((N, 3), np.int64)
+    entry = alloc((int(vox.shape[0]),), np.float64)
+    distance, depth, level = (alloc((N,), np.float64), alloc((N, 3), np.int64), alloc((B,), np.int64)) if R else (None, None, None)
+    counts = np.zeros(2, np.int64)
+    _G._check(_skeleton_lib().vmask_morphometry(dev, *shape, dist.data_ptr() if on_device else dist.ctypes.data, ptr(off) if B else None, B, ptr(vox), ptr(ends),
+                                    ptr(nodevox), N, h.ctypes.data, ptr(rt) if R else None, R, int(localSteps), ptr(bi), ptr(bf), ptr(radius), ptr(incident), ptr(entry),
+                                    ptr(distance) if R else None, ptr(depth) if R else None, ptr(level) if R else None, counts.ctypes.data))
+    raw = {'stepCounts': bi[:, 0:7], 'jumps': bi[:, 7], 'jumpOffset': bi[:, 8:14].reshape(B, 2, 3), 'radiusCount': bi[:, 14],
+           'endDir': bi[:, 15:21].reshape(B, 2, 3), 'chord': bi[:, 21:24], 'radiusSum': bf[:, 0], 'radiusDevSq': bf[:, 1], 'radiusMin': bf[:, 2],
+           'radiusMax': bf[:, 3], 'pathLength': bf[:, 4], 'nodeRadius': radius, 'entryRadius': entry,
+           'incidentBranch': incident >> 1, 'incidentEnd': (incident & 1) - 2 * (incident < 0)}      # (-1 stays -1 in both)
+    if R:
+        raw.update(pathDistance=distance, parentBranch=depth[:, 0], depthLevel=depth[:, 1], depthVoxel=depth[:, 2], branchLevel=level)
+    hraw = {k: np.ascontiguousarray(host(v)) for k, v in raw.items()}
+    derived = deriveMorphometry(hraw, host(off), host(ends), host(graph.nodeKind), h)
+    result = BranchMorphometry()
+    for k in MORPHOMETRY_DEPTH:
+        setattr(result, k, None)
+    for k, v in raw.items():
+        setattr(result, k, v.contiguous() if on_device else hraw[k])
+    for k, v in derived.items():
+        setattr(result, k, torch.as_tensor(v, device=tdev) if on_device else v)
+    result.spacing, result.localSteps, result.roots, result.depthRounds = h, int(localSteps), root_ix, int(counts[0])
+    if info is not None:
+        info['depthRounds'], info['levelRounds'] = int(counts[0]), int(counts[1])
+    return result
+
+
+def _plain(x):
+    """A numpy scalar or array as plain Python numbers and lists."""
+    return x.tolist() if hasattr(x, 'tolist') else x
+
+
+def writeMorphometry(graph, measured, baseFolder):
+    """The files of ``main(..., morphometry=True)`` for a host `BranchGraph` and its `BranchMorphometry`; returns their names.
+    ``branchMorphometry.npz``: every array of ``measured.names()``, ``names``, ``spacing``, ``localSteps``, ``roots``.
+    ``graphRepresentationWithEdgeInfo.graphml``: the graph of `writeGraphml` with the edge attributes pathLength, eculideanLength,
+    tortuosity, voxelLength, meanRadius, sigma and segmentIndex of the edge's branch, the node attribute radius at every voxel of a
+    branch, and depthVoxel / depthLevel / pathDistance at the reached node representatives.
+    ``segmentInfoDict.pkl`` (keyed by branch index, closed branches left out as graphRelated.py:64 does) and ``nodeInfoDict.pkl``
+    (keyed by coordinate tuple: every node representative) with the reference's key names and plain Python values, pickle
+    protocol 2."""
+    import pickle
+    m = measured
+    names = m.names()
+    np.savez_compressed(os.path.join(baseFolder, MORPHOMETRY_FILE), names=np.array(names), spacing=m.spacing, localSteps=np.int64(m.localSteps),
+                        roots=m.roots, depthRounds=np.int64(m.depthRounds), **{k: getattr(m, k) for k in names})
+    off = np.asarray(graph.offsets, np.int64)
+    B = len(off) - 1
+    ids = np.array([str(tuple(p)) for p in np.asarray(graph.coords).tolist()], dtype=object)
+    node_ids = [str(tuple(p)) for p in np.asarray(graph.nodeCoords).tolist()]
+    reached = m.depthLevel is not None
+    edge_keys = ('pathLength', 'eculideanLength', 'tortuosity', 'voxelLength', 'meanRadius', 'sigma')
+    columns = [_plain(getattr(m, k)) for k in edge_keys]
+    radius = dict(zip(ids.tolist(), m.entryRadius.tolist()))              # (a voxel in several branches has one radius)
+    depth = {}
+    if reached:
+        for v in np.flatnonzero(m.depthLevel >= 0).tolist():
+            depth[node_ids[v]] = (int(m.depthVoxel[v]), int(m.depthLevel[v]), float(m.pathDistance[v]))
+    edges = {}
+    for k in range(B):
+        seg = ids[off[k]:off[k + 1]].tolist()
+        for a, b in zip(seg[:-1], seg[1:]):
+            key = (a, b) if (b, a) not in edges else (b, a)               # (an undirected graph keeps one edge per pair: the last index wins)
+            edges[key] = k
+    with open(os.path.join(baseFolder, EDGE_INFO_GRAPH_FILE), 'w', encoding='utf-8') as f:
+        f.write('<?xml version=\'1.0\' encoding=\'utf-8\'?>\n')
+        f.write('<graphml xmlns="http://graphml.graphdrawing.org/xmlns" xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" '
+                'xsi:schemaLocation="http://graphml.graphdrawing.org/xmlns http://graphml.graphdrawing.org/xmlns/1.0/graphml.xsd">\n')
+        f.write('  <key id="d0" for="edge" attr.name="segmentIndex" attr.type="long" />\n')
+        for i, k in enumerate(edge_keys):
+            f.write('  <key id="d{}" for="edge" attr.name="{}" attr.type="{}" />\n'.format(i + 1, k, 'long' if k == 'voxelLength' else 'double'))
+        f.write('  <key id="d7" for="node" attr.name="radius" attr.type="double" />\n')
+        f.write('  <key id="d8" for="node" attr.name="depthVoxel" attr.type="long" />\n  <key id="d9" for="node" attr.name="depthLevel" attr.type="long" />\n')
+        f.write('  <key id="d10" for="node" attr.name="pathDistance" attr.type="double" />\n')
+        f.write('  <graph edgedefault="undirected">\n')
+        for a, r in radius.items():
+            f.write('    <node id="{}">\n      <data key="d7">{!r}</data>\n'.format(a, r))
+            if a in depth:
+                f.write('      <data key="d8">{}</data>\n      <data key="d9">{}</data>\n      <data key="d10">{!r}</data>\n'.format(*depth[a]))
+            f.write('    </node>\n')
+        for (a, b), k in edges.items():
+            f.write('    <edge source="{}" target="{}">\n      <data key="d0">{}</data>\n'.format(a, b, k))
+            for i, col in enumerate(columns):
+                f.write('      <data key="d{}">{!r}</data>\n'.format(i + 1, col[k]))
+            f.write('    </edge>\n')
+        f.write('  </graph>\n</graphml>\n')
+    ends = np.asarray(graph.branchEnds, np.int64).reshape(-1, 2)
+    segment_info = {}
+    for k in range(B):
+        if ends[k, 0] < 0 or (ends[k, 0] == ends[k, 1]):                  # (same head and tail)
+            continue
+        d = {key: col[k] for key, col in zip(edge_keys, columns)}
+        d['aspectRatio'] = float(m.aspectRatio[k])
+        d['type'] = 'terminating' if m.type[k] == 0 else 'bifurcating'
+        if reached and m.branchLevel[k] >= 0:
+            d['segmentLevel'] = int(m.branchLevel[k])
+        if not np.isnan(m.localBifurcationTorque[k]):
+            d['localBifurcationTorque'] = float(m.localBifurcationTorque[k])
+        segment_info[k] = d
+    node_info = {}
+    kinds, degrees = _plain(graph.nodeKind), _plain(graph.nodeDegree)
+    for v, c in enumerate(np.asarray(graph.nodeCoords).tolist()):
+        d = {'radius': float(m.nodeRadius[v])}
+        if kinds[v] == 0:
+            d['type'] = 'terminating'
+        elif degrees[v] >= 3:
+            d['type'] = 'bifurcating'
+        if node_ids[v] in depth:
+            d['depthVoxel'], d['depthLevel'], d['pathDistance'] = depth[node_ids[v]]
+        node_info[tuple(c)] = d
+    for row, v in enumerate(_plain(m.bifurcationNode)):
+        d = node_info[tuple(np.asarray(graph.nodeCoords)[v].tolist())]
+        for key in ('localBifurcationAmplitude', 'remoteBifurcationAmplitude', 'localBifurcationTilt', 'remoteBifurcationTilt', 'cubicLawResult',
+                    'squareLawResult', 'minRadiusRatio', 'maxRadiusRatio', 'lengthRatio'):
+            x = float(getattr(m, key)[row])
+            if not np.isnan(x):                                           # (an absent tilt is an absent key, as in the reference)
+                d[key] = x
+        r = [float(m.meanRadius[b]) for b in _plain(m.bifurcationBranches[row])]
+        d['radiusList'], d['minRadius'] = r, min(r)
+        d['normalVector'] = _plain(m.normalVector[row])
+    for name, obj in ((SEGMENT_INFO_FILE, segment_info), (NODE_INFO_FILE, node_info)):
+        with open(os.path.join(baseFolder, name), 'wb') as f:
+            pickle.dump(obj, f, protocol=2)
+    return [MORPHOMETRY_FILE, EDGE_INFO_GRAPH_FILE, SEGMENT_INFO_FILE, NODE_INFO_FILE]
+
+
 LABEL_FILE = 'segmentLabels.nii.gz'
 TERRITORY_FILE = 'segmentTerritories.npz'
 
@@ -462,7 +825,7 @@ def territoryVolumes(sizes, affine):
 DISTANCE_FILE = 'centrelineDistance.nii.gz'
 
 
-def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None):
+def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -478,7 +841,14 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     ``graphRepresentation.graphml`` hold its branches, ``branchGraph.npz`` the node and branch tables and the counts, and the
     territories are those of the pruned skeleton's branches.  A voxel of a junction cluster at which no branch ends occurs in no
     branch: as a site of the territories it has label 0, and the mask voxels nearest to it are counted in ``sizes[0]``.
-    ``prune=None`` writes every file as before."""
+    ``prune=None`` writes every file as before.
+    With ``morphometry=True`` as well (it needs `prune`; ``prune=(0, 0.0)`` prunes nothing) the branches are measured by
+    `branchMorphometry` - `dist` being the distance transform of the mask, the spacing the norms of the affine's columns, `roots`
+    node indices or coordinate triples - and `writeMorphometry` writes ``branchMorphometry.npz``,
+    ``graphRepresentationWithEdgeInfo.graphml``, ``segmentInfoDict.pkl`` and ``nodeInfoDict.pkl`` beside the others; every other
+    file and the returned values are those of a run without it."""
+    if morphometry and prune is None:
+        raise ValueError('morphometry=True needs prune (prune=(0, 0.0) prunes nothing)')
     if prune is not None and not segments:
         raise ValueError('prune needs segments=True')
     if territories and not segments:
@@ -514,6 +884,11 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     path = os.path.join(baseFolder, SEGMENT_FILE)
     saveSegmentList(segmentList, path)
     print('{} saved to {}.'.format(SEGMENT_FILE, path))
+    if morphometry:
+        spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
+        measured = branchMorphometry(graph, vesselVolumeMask=vesselVolumeMask, spacing=spacing, roots=roots)
+        for name in writeMorphometry(graph, measured, baseFolder):
+            print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if not territories:
         return skeleton, segmentList
     if geodesic:

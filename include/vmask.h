@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (DESIGN.md section 9 rows f5-f10): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f11): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -44,7 +44,15 @@
  *                      merged into one node, and short spurs pruned by a stated rule; DESIGN.md section 9, f10.  Claimed: exact
  *                      equality - skeleton, tables, counts - with the sequential model tests/branch_model.py; bit-identical
  *                      repeats.  Not claimed: pass-through clusters dissolved, agreement with the external tool's segments,
- *                      spur lengths in physical units, any per-branch quantity.
+ *                      spur lengths in physical units, any per-branch quantity (vmask_morphometry supplies those).
+ *   vmask_morphometry  what the reference's calculateBranchInfo (manualCorrectionGUI.py:215-385) and calculateProperty
+ *                      (graphRelated.py:35-400) compute with networkx and Python loops over every voxel of every segment: per
+ *                      branch the step counts that give its path length, the chord, the sums of the radius sample and the end
+ *                      directions; per node the radius and the three incident branches; from roots the path distance, the
+ *                      parent branch and the depth of every node; DESIGN.md section 9, f11.  Claimed: exact equality - every
+ *                      integer, the bits of every float64 sum - with the sequential model tests/morphometry_model.py;
+ *                      bit-identical repeats.  Not claimed: the reference's spline-based local directions and curvature,
+ *                      compartment partitioning, anything derived from these outputs (the Python layer's host formulas).
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -205,6 +213,62 @@ int vmask_branches(int device, const uint8_t* volume, int64_t n0, int64_t n1, in
                    uint8_t* skeleton /* may be NULL */, int64_t* counts,
                    int64_t* nodes, int64_t cap_node, int64_t* branch_ends, int64_t* offsets, int64_t cap_branch,
                    int64_t* voxels, int64_t cap_vox);
+
+/* Branch morphometry.  The shape of the volume; dist (float64 volume, non-negative, typically vmask_edt(mask)); the branch table
+ * that vmask_branches returned for a volume of that shape: offsets[nbranch + 1], voxels[offsets[nbranch]] (C-order linear
+ * indices), branch_ends[2 nbranch] (node ids, -1 -1 for a closed curve), node_voxel[nnode] (idx of the representatives).
+ * spacing (h0, h1, h2; NULL: 1 1 1; host or device), roots[nroots] (node ids, nroots >= 0), local_steps >= 1.
+ * Branch b has n = offsets[b + 1] - offsets[b] >= 2 entries e_0 .. e_(n-1); a pair is two consecutive entries, its offset
+ * d = e_(i+1) - e_i in voxel coordinates.
+ * branch_int (nbranch x 24, int64):
+ *   [0..6]   stepCounts: the pairs with (|d0|, |d1|, |d2|) in {0,1}^3 \ 0, at the class index 4 |d0| + 2 |d1| + |d2| - 1
+ *   [7]      jumps: every other pair (not 26-adjacent - the first or last pair inside a cluster that is no clique - or twice the
+ *            same voxel)
+ *   [8..13]  jumpOffset [2][3]: front = d of the pair (e_0, e_1) where it is a jump, back = d of the pair (e_(n-2), e_(n-1))
+ *            where it is a jump and n > 2; 0 0 0 otherwise.  A jump elsewhere is counted in [7] only.
+ *   [14]     radiusCount m: the radius sample is dist at the interior entries e_1 .. e_(n-2) for n >= 3 (m = n - 2), at both
+ *            entries for n == 2 (m = 2)
+ *   [15..20] endDir [2][3]: with k = min(local_steps, n - 1): e_k - e_0, then e_(n-1-k) - e_(n-1)
+ *   [21..23] chord: e_(n-1) - e_0
+ * branch_f64 (nbranch x 5, float64): [0] radiusSum, [1] radiusDevSq = sum of (r - mean)^2 with mean = fl(radiusSum / m),
+ *   [2] radiusMin, [3] radiusMax, [4] pathLength.
+ * THE ORDER OF THE TWO SUMS, for the values x_0 .. x_(m-1) in the sample's order (every operation one IEEE double operation,
+ * nothing contracted into an FMA, no floating-point atomics):
+ *   1. for j in [0, 64): a_j = ((x_j + x_(j+64)) + x_(j+128)) + ..; 0.0 where there is no x_j
+ *   2. for s = 32, 16, 8, 4, 2, 1: a_j <- a_j + a_(j xor s), all j at once
+ *   3. the sum is a_0.
+ * radiusDevSq sums fl(fl(x_i - mean) * fl(x_i - mean)) in the same order; a NaN result (an infinite radius) is stored as the
+ * quiet NaN 0x7ff8000000000000.  (A branch of at most 17 entries is summed by 16 lanes: steps 32 and 16 would add 0.0.)
+ * pathLength = ((..(0 + stepCounts[0] w_0) + ..) + stepCounts[6] w_6) + |front| + |back| on the host: w_c = sqrt((g0^2 + g1^2) +
+ * g2^2) with g_a = h_a where bit a of the class is set (d0 the bit of weight 4) and 0 elsewhere; a jump's length is the same
+ * expression of g_a = jumpOffset_a h_a.
+ * node_radius (nnode): dist[node_voxel].  incident (nnode x 3, int64): where exactly three branch ends meet at the node and
+ * they belong to three distinct branches: 2 branch + end (end 0: the branch starts here, 1: it ends here), ascending; -1 -1 -1
+ * otherwise.  entry_radius (offsets[nbranch], may be NULL): dist at every entry.
+ * With nroots > 0 (otherwise these three are not touched and may be NULL), w_b = pathLength[b]:
+ *   path_distance (nnode, float64): D(root) = 0; elsewhere D(v) = min over the branches b between u and v, u != v, of
+ *     fl(D(u) + w_b) - the least fixed point, which Dijkstra's algorithm computes with the same addition; +inf where no root is
+ *     reached.  Closed curves and loops on one node relax nothing.  Computed in rounds of one thread per branch with 64-bit
+ *     atomicMin on the bit patterns (non-negative doubles order as their bits) until a round lowers nothing; more than
+ *     max(nnode, 1) rounds: VRG_E_INTERNAL.
+ *   node_depth (nnode x 3, int64): [0] parentBranch = the smallest b with fl(D(u) + w_b) == D(v) and D(u) < D(v), -1 at roots
+ *     and unreached nodes; [1] depthLevel = depthLevel(u) + 1 and [2] depthVoxel = depthVoxel(u) + (n_b - 1) along
+ *     parentBranch, 0 at the roots, -1 at unreached nodes.
+ *   branch_level (nbranch): the larger depthLevel of the branch's ends, -1 where either is unreached or the branch has none.
+ * counts (2, may be NULL): [0] depthRounds (distance rounds run), [1] level rounds run - they describe the run, not the result.
+ * Everything else is a pure function of the inputs, bit-identical between runs.
+ * VRG_E_ARG, before anything is written: a spacing that is not finite and positive or with max / min > 1000 (as
+ * vmask_geodesic); local_steps < 1; a negative count; offsets that do not start at 0 or leave a branch fewer than two entries,
+ * a voxel outside the volume, an end or root that is no node id (counted on the device); a shape outside the envelope of the
+ * other passes.  VRG_E_MEM: dist and the tables where they are host arrays, 232 bytes per branch and 28 per node do not fit
+ * the device; everything allocated is freed. */
+int vmask_morphometry(int device, int64_t n0, int64_t n1, int64_t n2, const double* dist,
+                      const int64_t* offsets, int64_t nbranch, const int64_t* voxels, const int64_t* branch_ends,
+                      const int64_t* node_voxel, int64_t nnode, const double* spacing /* may be NULL */,
+                      const int64_t* roots, int64_t nroots, int64_t local_steps,
+                      int64_t* branch_int, double* branch_f64, double* node_radius, int64_t* incident,
+                      double* entry_radius /* may be NULL */,
+                      double* path_distance, int64_t* node_depth, int64_t* branch_level, int64_t* counts /* may be NULL */);
 
 const char* vmask_last_error(void);
 
