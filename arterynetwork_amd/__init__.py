@@ -7,7 +7,9 @@ from .variationalRegionGrowing import variationalRegionGrowing  # noqa: F401
 from .vesselness import vesselnessFilter, sigmasFromDiameters  # noqa: F401
 from .skeletonization import branchTerritories, territoryVolumes, geodesicTerritories  # noqa: F401
 from .skeletonization import branchMorphometry, BranchMorphometry, deriveMorphometry, pathLengths, writeMorphometry  # noqa: F401
+from .skeletonization import partitionCompartments, Compartments, compartmentTerritories, compartmentSummary, writeCompartments  # noqa: F401
 from .geodesic import geodesicDistance  # noqa: F401
 
 __all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'branchTerritories', 'territoryVolumes',
-           'geodesicTerritories', 'geodesicDistance', 'branchMorphometry', 'BranchMorphometry', 'deriveMorphometry', 'pathLengths', 'writeMorphometry']
+           'geodesicTerritories', 'geodesicDistance', 'branchMorphometry', 'BranchMorphometry', 'deriveMorphometry', 'pathLengths', 'writeMorphometry',
+           'partitionCompartments', 'Compartments', 'compartmentTerritories', 'compartmentSummary', 'writeCompartments']

@@ -42,6 +42,12 @@ path length, the chord, the tortuosity and the radius statistics, per node the r
 the radius laws, and from roots the path distance and depth of every node.  ``main(..., segments=True, prune=(3, 1.0),
 morphometry=True)`` writes ``branchMorphometry.npz``, ``graphRepresentationWithEdgeInfo.graphml``, ``segmentInfoDict.pkl`` and
 ``nodeInfoDict.pkl`` from it.
+
+``partitionCompartments`` (``vmask_compartments``: DESIGN.md section 9, "f12 compartments") is the reference's compartment
+partition: the graph walked from every compartment's initial voxels, never onto one of its boundary voxels; every vertex and
+branch gets its compartment, depth and level.  ``compartmentTerritories`` carries the compartments back to the voxels of the
+mask, ``compartmentSummary`` groups the morphometry by them, and ``main(..., segments=True, prune=(3, 1.0), compartments=...)``
+writes ``partitionInfo.pkl`` and ``compartments.npz``.
 """
 from __future__ import annotations
 
@@ -111,6 +117,7 @@ def _skeleton_lib():
         dll.vmask_territories.argtypes = [C.c_int, p, p, i64, i64, i64, p, i64, p, p, p, p]
         dll.vmask_branches.argtypes = [C.c_int, p, i64, i64, i64, i64, C.c_double, p, i64, p, p, p, i64, p, p, i64, p, i64]
         dll.vmask_morphometry.argtypes = [C.c_int, i64, i64, i64, p, p, i64, p, p, p, i64, p, p, i64, i64, p, p, p, p, p, p, p, p, p]
+        dll.vmask_compartments.argtypes = [C.c_int, i64, i64, i64, p, i64, p, p, p, i64, i64, p, p, p, p] + [p] * 10
     return dll
 
 
@@ -608,7 +615,7 @@ def _plain(x):
     return x.tolist() if hasattr(x, 'tolist') else x
 
 
-def writeMorphometry(graph, measured, baseFolder):
+def writeMorphometry(graph, measured, baseFolder, parts=None):
     """The files of ``main(..., morphometry=True)`` for a host `BranchGraph` and its `BranchMorphometry`; returns their names.
     ``branchMorphometry.npz``: every array of ``measured.names()``, ``names``, ``spacing``, ``localSteps``, ``roots``.
     ``graphRepresentationWithEdgeInfo.graphml``: the graph of `writeGraphml` with the edge attributes pathLength, eculideanLength,
@@ -616,7 +623,8 @@ def writeMorphometry(graph, measured, baseFolder):
     branch, and depthVoxel / depthLevel / pathDistance at the reached node representatives.
     ``segmentInfoDict.pkl`` (keyed by branch index, closed branches left out as graphRelated.py:64 does) and ``nodeInfoDict.pkl``
     (keyed by coordinate tuple: every node representative) with the reference's key names and plain Python values, pickle
-    protocol 2."""
+    protocol 2.  With `parts` (a `Compartments` of host arrays) the entries of owned branches and nodes gain ``partitionName``, and
+    the segments ``segmentLevel`` - the partition's, as graphRelated.py:72-74,108-110 reads them."""
     import pickle
     m = measured
     names = m.names()
@@ -674,6 +682,8 @@ def writeMorphometry(graph, measured, baseFolder):
             d['segmentLevel'] = int(m.branchLevel[k])
         if not np.isnan(m.localBifurcationTorque[k]):
             d['localBifurcationTorque'] = float(m.localBifurcationTorque[k])
+        if parts is not None and parts.branchCompartment[k]:
+            d['partitionName'], d['segmentLevel'] = parts.names[int(parts.branchCompartment[k]) - 1], int(parts.branchLevel[k])
         segment_info[k] = d
     node_info = {}
     kinds, degrees = _plain(graph.nodeKind), _plain(graph.nodeDegree)
@@ -685,6 +695,8 @@ def writeMorphometry(graph, measured, baseFolder):
             d['type'] = 'bifurcating'
         if node_ids[v] in depth:
             d['depthVoxel'], d['depthLevel'], d['pathDistance'] = depth[node_ids[v]]
+        if parts is not None and parts.nodeCompartment[v]:
+            d['partitionName'] = parts.names[int(parts.nodeCompartment[v]) - 1]
         node_info[tuple(c)] = d
     for row, v in enumerate(_plain(m.bifurcationNode)):
         d = node_info[tuple(np.asarray(graph.nodeCoords)[v].tolist())]
@@ -700,6 +712,224 @@ def writeMorphometry(graph, measured, baseFolder):
         with open(os.path.join(baseFolder, name), 'wb') as f:
             pickle.dump(obj, f, protocol=2)
     return [MORPHOMETRY_FILE, EDGE_INFO_GRAPH_FILE, SEGMENT_INFO_FILE, NODE_INFO_FILE]
+
+
+PARTITION_FILE = 'partitionInfo.pkl'
+COMPARTMENT_FILE = 'compartments.npz'
+COMPARTMENT_LABEL_FILE = 'compartmentLabels.nii.gz'
+COMPARTMENT_ARRAYS = ('entryCompartment', 'entryDepth', 'entryLevel', 'nodeCompartment', 'nodeDepth', 'nodeLevel', 'branchCompartment', 'branchLevel',
+                      'compartmentCounts')
+
+
+class Compartments:
+    """What `partitionCompartments` returns: ``names`` (labels 1 .. K in this order) and one attribute per name of
+    `COMPARTMENT_ARRAYS` - per entry of ``graph.coords``, per node and per branch the owning compartment (uint8, 0: none) and the
+    depth and level in it (int64, -1 without an owner); ``compartmentCounts`` (int64, (K + 1) x 3: vertices owned, vertices
+    reached, branches; row 0: owned by none, reached by two or more, the remaining branches).  ``nodeKind`` is the graph's (host),
+    ``depthRounds`` / ``levelRounds`` describe the run."""
+
+    def __init__(self, names, nodeKind, **arrays):
+        self.names, self.nodeKind = list(names), nodeKind
+        for k in COMPARTMENT_ARRAYS:
+            setattr(self, k, arrays[k])
+
+    def partitionInfo(self, graph):
+        """The reference's ``partitionInfo`` (partitionCompartmentGUIDetail.py:316-343): ``{name: {'visitedVoxels': [tuples],
+        'segmentIndexList': [ints]}}``.  ``visitedVoxels`` holds the voxels of the vertices the compartment owns, every vertex once,
+        ascending by depth and then by the index of its first entry; ``segmentIndexList`` the branches that belong to it, ascending."""
+        host = lambda a: np.asarray(a.cpu() if _G._on_device(a) else a)
+        off, ends = host(graph.offsets).astype(np.int64), host(graph.branchEnds).astype(np.int64).reshape(-1, 2)
+        coords = host(graph.coords).reshape(-1, 3)
+        comp, depth, bcomp = host(self.entryCompartment), host(self.entryDepth), host(self.branchCompartment)
+        E = len(comp)
+        # one entry per vertex: the first at which it occurs (a node at several branch ends, a closed branch's vertex at both of its ends)
+        vertex = np.arange(E, dtype=np.int64)
+        if len(off) > 1:
+            first, last = off[:-1], off[1:] - 1
+            is_open = ends[:, 0] >= 0
+            vertex[first[is_open]], vertex[last[is_open]] = E + ends[is_open, 0], E + ends[is_open, 1]
+            vertex[last[~is_open]] = first[~is_open]
+        _, once = np.unique(vertex, return_index=True)                    # (the first occurrence of every vertex)
+        info = {}
+        for k, name in enumerate(self.names):
+            mine = once[comp[once] == k + 1]
+            mine = mine[np.lexsort((mine, depth[mine]))]
+            info[name] = {'visitedVoxels': [tuple(c) for c in coords[mine].tolist()], 'segmentIndexList': np.flatnonzero(bcomp == k + 1).tolist()}
+        return info
+
+
+def _compartment_lists(graph, compartments):
+    """``(names, [(initial indices, boundary indices), ..])`` as C-order linear indices from either form of `compartments`."""
+    if isinstance(compartments, dict):
+        names = [str(k) for k in compartments]
+        pairs = [(v['initialVoxels'], v['boundaryVoxels']) for v in compartments.values()]
+    else:
+        pairs = [tuple(pr) for pr in compartments]
+        if any(len(pr) != 2 for pr in pairs):
+            raise ValueError('compartments: a dict in the layout of chosenVoxelsForPartition.pkl or a sequence of (initial, boundary) pairs')
+        names = [str(k + 1) for k in range(len(pairs))]
+    if not 1 <= len(pairs) <= 255:
+        raise ValueError('1 to 255 compartments, not {}'.format(len(pairs)))
+    host = lambda a: np.asarray(a.cpu() if _G._on_device(a) else a)
+    shape = tuple(int(k) for k in graph.skeleton.shape)
+    nc = host(graph.nodeCoords).astype(np.int64).reshape(-1, 3)
+    lin = lambda c: (c[:, 0] * shape[1] + c[:, 1]) * shape[2] + c[:, 2]
+    vertices = set(lin(host(graph.coords).astype(np.int64).reshape(-1, 3)).tolist()) | set(lin(nc).tolist())
+    skeleton = None
+
+    def index_of(item):
+        nonlocal skeleton
+        if np.ndim(item) == 0:
+            k = int(item)
+            if not 0 <= k < len(nc):
+                raise ValueError('{} is no node index (the graph has {} nodes)'.format(k, len(nc)))
+            return int(lin(nc[k:k + 1])[0])
+        if len(item) != 3:
+            raise ValueError('a listed voxel is a node index or a coordinate triple')
+        c = tuple(int(x) for x in item)
+        if not all(0 <= x < n for x, n in zip(c, shape)):
+            raise ValueError('voxel {} lies outside the volume {}'.format(c, shape))
+        v = (c[0] * shape[1] + c[1]) * shape[2] + c[2]
+        if v not in vertices:
+            if skeleton is None:
+                skeleton = host(graph.skeleton)
+            if skeleton[c]:
+                raise ValueError('voxel {} is a skeleton voxel but no entry of the branch table: a member of a junction cluster other '
+                                 'than its representative, or an isolated voxel'.format(c))
+            raise ValueError('voxel {} is no voxel of the centre line'.format(c))
+        return v
+    as_items = lambda x: list(x.tolist() if hasattr(x, 'tolist') else x)
+    return names, [(np.array([index_of(i) for i in as_items(a)], np.int64), np.array([index_of(i) for i in as_items(b)], np.int64)) for a, b in pairs]
+
+
+def partitionCompartments(graph, compartments, device=0, info=None):
+    """The compartment partition of a `BranchGraph` (``vmask_compartments``, DESIGN.md section 9, "f12 compartments") as a
+    `Compartments`.  `compartments`: the reference's ``chosenVoxelsForPartition.pkl`` layout ``{name: {'initialVoxels': [..],
+    'boundaryVoxels': [..]}}`` - insertion order gives the labels 1 .. K - or a sequence of ``(initial, boundary)`` pairs, named
+    '1' .. 'K'; an item is a coordinate triple or a scalar node index (as `branchMorphometry`'s roots).  ``ValueError`` for a
+    coordinate that is the voxel of no vertex.
+    The vertices are the nodes, the interior entries of the branches and one vertex per closed branch; consecutive entries are
+    joined.  Compartment c reaches what a path from one of its initial vertices reaches without a vertex on one of its boundary
+    voxels; depth = the fewest edges of such a path (the reference's depthVoxel), level = 0 at the initial vertices and, elsewhere,
+    the smallest level of a neighbour one edge nearer, plus one at a node (depthLevel on trees).  A vertex belongs to the
+    compartment of smallest (depth, label) that reaches it, a branch to the compartment that owns every one of its entries
+    (segmentIndexList on trees), its level being the smallest of its entries' (segmentLevel).
+    A host graph gives host arrays, a graph of tensors on the GPU gives tensors on the same device.  `info`, when a dict,
+    receives ``depthRounds`` and ``levelRounds``."""
+    names, lists = _compartment_lists(graph, compartments)
+    K = len(lists)
+    on_device = _G._on_device(graph.offsets)
+    shape = tuple(int(k) for k in graph.skeleton.shape)
+    n1, n2 = shape[1], shape[2]
+    B, N = int(graph.offsets.shape[0]) - 1, int(graph.nodeCoords.shape[0])
+    ioff = np.concatenate(([0], np.cumsum([len(a) for a, _ in lists]))).astype(np.int64)
+    boff = np.concatenate(([0], np.cumsum([len(b) for _, b in lists]))).astype(np.int64)
+    ivox = np.ascontiguousarray(np.concatenate([a for a, _ in lists]), dtype=np.int64)
+    bvox = np.ascontiguousarray(np.concatenate([b for _, b in lists]), dtype=np.int64)
+    if on_device:
+        import torch
+        tdev = graph.offsets.device
+        dev = _G._dev_index(graph.offsets)
+        lin = lambda c: ((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2]).to(torch.int64).contiguous()
+        off, ends = graph.offsets.to(torch.int64).contiguous(), graph.branchEnds.to(torch.int64).contiguous()
+        alloc = lambda shp, dt: torch.empty(shp, dtype=torch.uint8 if dt is np.uint8 else torch.int64, device=tdev)
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        kind = graph.nodeKind.cpu().numpy()
+        torch.cuda.synchronize(tdev)
+    else:
+        dev = device
+        lin = lambda c: np.ascontiguousarray((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2], dtype=np.int64)
+        off, ends = np.ascontiguousarray(graph.offsets, dtype=np.int64), np.ascontiguousarray(graph.branchEnds, dtype=np.int64)
+        alloc = lambda shp, dt: np.empty(shp, dt)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        kind = np.asarray(graph.nodeKind)
+    vox, nodevox = lin(graph.coords.reshape(-1, 3)), lin(graph.nodeCoords.reshape(-1, 3))
+    E = int(vox.shape[0])
+    out = {'entryCompartment': alloc((E,), np.uint8), 'entryDepth': alloc((E,), np.int64), 'entryLevel': alloc((E,), np.int64),
+           'nodeCompartment': alloc((N,), np.uint8), 'nodeDepth': alloc((N,), np.int64), 'nodeLevel': alloc((N,), np.int64),
+           'branchCompartment': alloc((B,), np.uint8), 'branchLevel': alloc((B,), np.int64), 'compartmentCounts': alloc((K + 1, 3), np.int64)}
+    counts = np.zeros(2, np.int64)
+    _G._check(_skeleton_lib().vmask_compartments(dev, *shape, ptr(off) if B else None, B, ptr(vox), ptr(ends), ptr(nodevox), N, K, ioff.ctypes.data,
+                                                 ivox.ctypes.data if ivox.size else None, boff.ctypes.data, bvox.ctypes.data if bvox.size else None,
+                                                 *(ptr(out[k]) for k in COMPARTMENT_ARRAYS[:8]), out['compartmentCounts'].data_ptr() if on_device else
+                                                 out['compartmentCounts'].ctypes.data, counts.ctypes.data))
+    parts = Compartments(names, kind, **out)
+    parts.depthRounds, parts.levelRounds = int(counts[0]), int(counts[1])
+    if info is not None:
+        info['depthRounds'], info['levelRounds'] = int(counts[0]), int(counts[1])
+    return parts
+
+
+def compartmentTerritories(vesselVolumeMask, graph, parts, spacing=None, device=0, info=None, return_distance=False):
+    """The compartments carried back to the voxels: ``labels`` (uint8, the mask's shape) and ``sizes`` (int64, K + 1).  The seeds
+    are the entries of ``graph.coords`` that a compartment owns and that lie in the mask, labelled by their owner; a voxel with
+    ``vesselVolumeMask != 0`` gets the label of the seed at the smallest path length inside the mask (`geodesic.geodesicDistance`
+    with these seeds: steps in `spacing`, ties to the smallest label), 0 outside the mask and where no seed is reached.
+    ``sizes.sum()`` is the mask's voxel count.  ``return_distance=True`` adds ``distance`` (float64).  A mask tensor on the GPU gives
+    tensors on the same device.  `info`, when a dict, receives the counts of `geodesic.geodesicDistance`."""
+    on_device = _G._on_device(vesselVolumeMask)
+    K = len(parts.names)
+    if on_device:
+        import torch
+        m = _G._u8t(vesselVolumeMask)
+        as_t = lambda a: a if _G._on_device(a) else torch.as_tensor(np.asarray(a), device=m.device)
+        co, lab = as_t(graph.coords).to(torch.int64).reshape(-1, 3), as_t(parts.entryCompartment).to(torch.int32)
+    else:
+        m = _G._u8c(vesselVolumeMask)
+        host = lambda a: np.asarray(a.cpu() if _G._on_device(a) else a)
+        co, lab = host(graph.coords).astype(np.int64).reshape(-1, 3), host(parts.entryCompartment).astype(np.int32)
+    if tuple(m.shape) != tuple(int(k) for k in graph.skeleton.shape):
+        raise ValueError('the graph\'s skeleton and vesselVolumeMask must have the same shape')
+    vox = (co[:, 0] * int(m.shape[1]) + co[:, 1]) * int(m.shape[2]) + co[:, 2]
+    keep = (lab > 0) & (m.reshape(-1)[vox] != 0)
+    vox, lab = vox[keep], lab[keep]
+    if on_device:
+        vox, lab = vox.contiguous(), lab.contiguous()
+    else:
+        vox, lab = np.ascontiguousarray(vox), np.ascontiguousarray(lab)
+    distance, labels, sizes = _geo._run(m, vox, lab, K, spacing, device, return_distance, True, info)
+    labels = labels.to(torch.uint8) if on_device else labels.astype(np.uint8)
+    return (labels, sizes, distance) if return_distance else (labels, sizes)
+
+
+def compartmentSummary(parts, measured=None, sizes=None, affine=None):
+    """Per compartment name a dict: ``branches`` (the branches that belong to it), ``terminalNodes`` (the end points it owns) and
+    ``maxLevel`` (the largest ``branchLevel`` of its branches, -1 without one); with a `BranchMorphometry` ``totalLength``
+    (``math.fsum`` of ``pathLength`` over its branches: exactly rounded, whatever the order) and ``meanRadius`` (the mean of the
+    branches' ``meanRadius``, NaN without a branch); with `sizes` (of `compartmentTerritories`) and `affine` ``volume``
+    (`territoryVolumes`)."""
+    import math
+    host = lambda a: np.asarray(a.cpu() if _G._on_device(a) else a)
+    bcomp, blevel, ncomp, kind = host(parts.branchCompartment), host(parts.branchLevel), host(parts.nodeCompartment), np.asarray(parts.nodeKind)
+    volumes = territoryVolumes(host(sizes), affine if affine is not None else np.eye(4)) if sizes is not None else None
+    out = {}
+    for k, name in enumerate(parts.names):
+        mine = np.flatnonzero(bcomp == k + 1)
+        d = {'branches': int(len(mine)), 'terminalNodes': int(np.count_nonzero((ncomp == k + 1) & (kind == 0))),
+             'maxLevel': int(blevel[mine].max()) if len(mine) else -1}
+        if measured is not None:
+            d['totalLength'] = math.fsum(host(measured.pathLength)[mine].tolist())
+            d['meanRadius'] = float(np.mean(host(measured.meanRadius)[mine])) if len(mine) else float('nan')
+        if volumes is not None:
+            d['volume'] = float(volumes[k + 1])
+        out[name] = d
+    return out
+
+
+def writeCompartments(graph, parts, baseFolder, measured=None, sizes=None, affine=None):
+    """``partitionInfo.pkl`` (`Compartments.partitionInfo`, pickle protocol 2) and ``compartments.npz``: ``names``, every array of
+    `COMPARTMENT_ARRAYS`, the columns of `compartmentSummary` as ``summary_<key>`` (one value per compartment) and, with `sizes`,
+    ``sizes`` and ``volumes``; returns the two file names."""
+    import pickle
+    with open(os.path.join(baseFolder, PARTITION_FILE), 'wb') as f:
+        pickle.dump(parts.partitionInfo(graph), f, protocol=2)
+    summary = compartmentSummary(parts, measured, sizes, affine)
+    keys = list(summary[parts.names[0]])
+    extra = {'summary_' + k: np.array([summary[n][k] for n in parts.names]) for k in keys}
+    if sizes is not None:
+        extra.update(sizes=np.asarray(sizes), volumes=territoryVolumes(sizes, affine))
+    np.savez_compressed(os.path.join(baseFolder, COMPARTMENT_FILE), names=np.array(parts.names), **{k: getattr(parts, k) for k in COMPARTMENT_ARRAYS}, **extra)
+    return [PARTITION_FILE, COMPARTMENT_FILE]
 
 
 LABEL_FILE = 'segmentLabels.nii.gz'
@@ -825,7 +1055,7 @@ def territoryVolumes(sizes, affine):
 DISTANCE_FILE = 'centrelineDistance.nii.gz'
 
 
-def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None):
+def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -846,7 +1076,16 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     `branchMorphometry` - `dist` being the distance transform of the mask, the spacing the norms of the affine's columns, `roots`
     node indices or coordinate triples - and `writeMorphometry` writes ``branchMorphometry.npz``,
     ``graphRepresentationWithEdgeInfo.graphml``, ``segmentInfoDict.pkl`` and ``nodeInfoDict.pkl`` beside the others; every other
-    file and the returned values are those of a run without it."""
+    file and the returned values are those of a run without it.
+    With `compartments` as well (it needs `prune`): a dict in the layout of the reference's ``chosenVoxelsForPartition.pkl``, or the
+    path of such a file.  `partitionCompartments` divides the branch graph, and ``partitionInfo.pkl`` and ``compartments.npz``
+    (`writeCompartments`) are written; with ``territories=True`` also ``compartmentLabels.nii.gz`` (uint8, the mask's affine:
+    `compartmentTerritories` in the affine's spacing) and the territories' ``sizes`` and ``volumes`` into the npz; with
+    ``morphometry=True`` the entries of ``segmentInfoDict.pkl`` / ``nodeInfoDict.pkl`` of owned branches and nodes gain
+    ``partitionName``, the segments ``segmentLevel``.  The returned values are those of a run without it; without `compartments`
+    every file is what it was."""
+    if compartments is not None and prune is None:
+        raise ValueError('compartments needs prune (prune=(0, 0.0) prunes nothing)')
     if morphometry and prune is None:
         raise ValueError('morphometry=True needs prune (prune=(0, 0.0) prunes nothing)')
     if prune is not None and not segments:
@@ -884,10 +1123,27 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     path = os.path.join(baseFolder, SEGMENT_FILE)
     saveSegmentList(segmentList, path)
     print('{} saved to {}.'.format(SEGMENT_FILE, path))
+    parts = measured = None
+    if compartments is not None:
+        if isinstance(compartments, (str, bytes, os.PathLike)):
+            import pickle
+            with open(compartments, 'rb') as f:
+                compartments = pickle.load(f)
+        parts = partitionCompartments(graph, compartments)
     if morphometry:
         spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
         measured = branchMorphometry(graph, vesselVolumeMask=vesselVolumeMask, spacing=spacing, roots=roots)
-        for name in writeMorphometry(graph, measured, baseFolder):
+        for name in (writeMorphometry(graph, measured, baseFolder) if parts is None else writeMorphometry(graph, measured, baseFolder, parts=parts)):
+            print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
+    if parts is not None:
+        compartmentSizes = None
+        if territories:
+            spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
+            compartmentLabels, compartmentSizes = compartmentTerritories(vesselVolumeMask, graph, parts, spacing=spacing)
+            path = os.path.join(baseFolder, COMPARTMENT_LABEL_FILE)
+            saveVolume(compartmentLabels, affine, path, astype=np.uint8)
+            print('{} saved to {}.'.format(COMPARTMENT_LABEL_FILE, path))
+        for name in writeCompartments(graph, parts, baseFolder, measured, compartmentSizes, affine):
             print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if not territories:
         return skeleton, segmentList

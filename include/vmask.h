@@ -52,7 +52,14 @@
  *                      parent branch and the depth of every node; DESIGN.md section 9, f11.  Claimed: exact equality - every
  *                      integer, the bits of every float64 sum - with the sequential model tests/morphometry_model.py;
  *                      bit-identical repeats.  Not claimed: the reference's spline-based local directions and curvature,
- *                      compartment partitioning, anything derived from these outputs (the Python layer's host formulas).
+ *                      anything derived from these outputs (the Python layer's host formulas).
+ *   vmask_compartments the reference's compartment partition (myFunctions.randomWalkBFS, partitionCompartmentGUIDetail.py:316-343):
+ *                      the branch graph walked from every compartment's initial voxels without stepping onto one of its boundary
+ *                      voxels - per entry, node and branch the owning compartment, the depth and the level; DESIGN.md section 9,
+ *                      f12.  Claimed: exact equality - every output is an integer - with the sequential model
+ *                      tests/compartment_model.py; bit-identical repeats.  Not claimed: the reference's list order, its
+ *                      order-dependent depthLevel and segmentIndexList in loops, voxels of a cluster other than the
+ *                      representative, per-compartment flow quantities.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -269,6 +276,53 @@ int vmask_morphometry(int device, int64_t n0, int64_t n1, int64_t n2, const doub
                       int64_t* branch_int, double* branch_f64, double* node_radius, int64_t* incident,
                       double* entry_radius /* may be NULL */,
                       double* path_distance, int64_t* node_depth, int64_t* branch_level, int64_t* counts /* may be NULL */);
+
+/* The compartment partition: a bounded traversal of the branch graph.  The branch table is what vmask_branches returned for a
+ * volume of the given shape (offsets[nbranch + 1], voxels[E], E = offsets[nbranch], branch_ends[2 nbranch], node_voxel[nnode]);
+ * branch b has n_b >= 2 entries.
+ * Vertices: the nnode nodes; every interior entry (b, i), 0 < i < n_b - 1; one private vertex per closed branch (ends -1 -1),
+ * whose first and last entry are the same voxel.  Entry (b, 0) IS the node branch_ends[b][0], entry (b, n_b - 1) IS the node
+ * branch_ends[b][1].  Edges: consecutive entries of a branch (a jump pair inside a cluster is one edge like any other).  The
+ * voxel of a node is its representative; the other members of a junction cluster are no vertices.
+ * Compartment c = 1 .. ncomp (1 <= ncomp <= 255) has two lists of C-order linear indices, the initial voxels
+ * init_vox[init_off[c - 1] .. init_off[c]) and the boundary voxels bound_vox[bound_off[c - 1] .. bound_off[c]); duplicates are
+ * allowed, an empty initial list reaches nothing.  A vertex is blocked in c when its voxel is a boundary voxel of c, initial
+ * when it is an initial voxel of c.
+ *   d_c(x)  the fewest edges from an initial vertex to x over paths with no blocked vertex; x is reached by c when there is one
+ *           (the reference's depthVoxel; the reached set is its visitedVoxels as a set)
+ *   l_c(x)  0 at the initial vertices; elsewhere the minimum over the unblocked neighbours y with d_c(y) = d_c(x) - 1 of
+ *           l_c(y) + [x is a node] - end points count as nodes, a closed branch's private vertex does not.  On a tree this is
+ *           the reference's depthLevel; in a loop the reference's value depends on list order, this one is the stated minimum.
+ * Owner of a vertex: the c with the smallest (d_c(x), c) among those that reach it, 0 where none does.  Branch b belongs to c
+ * when every one of its entries is owned by c (the reference's segmentIndexList on trees; a branch cut by a boundary voxel
+ * belongs to nobody); its level is the minimum level of its entries (segmentLevel).  ncomp = 1 is the reference's independent
+ * traversal of that compartment.
+ * entry_comp / entry_depth / entry_level (E each), node_comp / node_depth / node_level (nnode each): the owner, and the depth
+ * and level in the owner; -1 -1 without an owner.  branch_comp / branch_level (nbranch each): -1 where branch_comp is 0.
+ * comp_counts ((ncomp + 1) x 3): row c: [0] vertices owned by c, [1] vertices reached by c, [2] branches with branch_comp == c;
+ * row 0: [0] vertices owned by none, [1] vertices reached by two or more compartments, [2] all remaining branches.
+ * counts (2, may be NULL): the depth rounds and the level rounds run - they describe the run, not the result.  Everything else
+ * is a pure function of the inputs, bit-identical between runs.
+ * Per (compartment, branch) pair one thread: a pass over the branch finds whether it has a blocked entry and the hops from
+ * its initial entries to either end; the nodes' depths settle in label-correcting rounds with 64-bit integer atomicMin until
+ * a round lowers nothing, then the levels over the tight predecessors in the same way (more than max(nnode, 1) + 1 rounds:
+ * VRG_E_INTERNAL); a walk per pair fills the entries between the ends and the initial entries; the compartments are merged by
+ * the key (depth, c).  No floating point.
+ * VRG_E_ARG, before anything is written: ncomp outside [1, 255]; a list offset table that does not ascend from 0 (looked at on
+ * the host: it says how much is read); and, counted on the device: a listed index outside the volume, a listed voxel that is
+ * the voxel of no vertex, a voxel in both lists of one compartment, the table errors that vmask_morphometry refuses,
+ * voxels[offsets[b]] != node_voxel[branch_ends[b][0]] and likewise at the last entry, a closed branch whose first and last
+ * entry differ; a shape outside the envelope of the other passes.
+ * VRG_E_MEM: the tables and outputs where they are host arrays, 17 bytes per (compartment, branch), 17 per (compartment, node)
+ * and one per entry do not fit the device; everything allocated is freed. */
+int vmask_compartments(int device, int64_t n0, int64_t n1, int64_t n2,
+                       const int64_t* offsets, int64_t nbranch, const int64_t* voxels, const int64_t* branch_ends,
+                       const int64_t* node_voxel, int64_t nnode,
+                       int64_t ncomp, const int64_t* init_off, const int64_t* init_vox, const int64_t* bound_off, const int64_t* bound_vox,
+                       uint8_t* entry_comp, int64_t* entry_depth, int64_t* entry_level,      /* E each */
+                       uint8_t* node_comp, int64_t* node_depth, int64_t* node_level,         /* nnode each */
+                       uint8_t* branch_comp, int64_t* branch_level,                          /* nbranch each */
+                       int64_t* comp_counts /* (ncomp + 1) x 3 */, int64_t* counts /* 2, may be NULL */);
 
 const char* vmask_last_error(void);
 
