@@ -9,7 +9,9 @@ from .skeletonization import branchTerritories, territoryVolumes, geodesicTerrit
 from .skeletonization import branchMorphometry, BranchMorphometry, deriveMorphometry, pathLengths, writeMorphometry  # noqa: F401
 from .skeletonization import partitionCompartments, Compartments, compartmentTerritories, compartmentSummary, writeCompartments  # noqa: F401
 from .geodesic import geodesicDistance  # noqa: F401
+from .flow import simulateFlow, FlowResult, branchResistance, terminalPressures, referenceResiduals  # noqa: F401
 
 __all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'branchTerritories', 'territoryVolumes',
            'geodesicTerritories', 'geodesicDistance', 'branchMorphometry', 'BranchMorphometry', 'deriveMorphometry', 'pathLengths', 'writeMorphometry',
-           'partitionCompartments', 'Compartments', 'compartmentTerritories', 'compartmentSummary', 'writeCompartments']
+           'partitionCompartments', 'Compartments', 'compartmentTerritories', 'compartmentSummary', 'writeCompartments',
+           'simulateFlow', 'FlowResult', 'branchResistance', 'terminalPressures', 'referenceResiduals']

@@ -102,6 +102,14 @@ def product_lib():
     return _product
 
 
+def bind_flow(dll):
+    """The argument types of ``vmask_flow`` (include/vmask.h) on a loaded library; returns the library."""
+    if not getattr(dll.vmask_flow, 'argtypes', None):
+        p, i64, f64 = C.c_void_p, C.c_int64, C.c_double
+        dll.vmask_flow.argtypes = [C.c_int, i64, i64, p, p, i64, p, i64, p, i64, f64, f64, i64, p, p, p, p, p]
+    return dll
+
+
 def _as_supported(a):
     """Return an array with a dtype the C-ABI understands and C- or F-contiguous memory."""
     a = np.asarray(a)

@@ -48,6 +48,11 @@ partition: the graph walked from every compartment's initial voxels, never onto 
 branch gets its compartment, depth and level.  ``compartmentTerritories`` carries the compartments back to the voxels of the
 mask, ``compartmentSummary`` groups the morphometry by them, and ``main(..., segments=True, prune=(3, 1.0), compartments=...)``
 writes ``partitionInfo.pkl`` and ``compartments.npz``.
+
+``flowOnGraph`` (``vmask_flow`` through `flow.simulateFlow`: DESIGN.md section 9, "f13 flow") is the reference's flow stage on the
+measured graph: the roots held at the inlet pressure, every reached end point at its terminal pressure, Hazen-Williams
+resistances from ``pathLength`` and ``meanRadius``; ``main(..., morphometry=True, roots=..., flow=dict(...))`` writes
+``flowResult.npz`` and the ``simulationData`` entries of the two info files.
 """
 from __future__ import annotations
 
@@ -1055,7 +1060,58 @@ def territoryVolumes(sizes, affine):
 DISTANCE_FILE = 'centrelineDistance.nii.gz'
 
 
-def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None):
+def flowOnGraph(graph, measured, spacing, pressureIn, slope, c, k=1.852, metresPerUnit=1e-3, factor=0.8, inlet=None, tol=1e-10, maxIter=50, device=0):
+    """The flow solve of ``main(..., flow=...)`` on a host `BranchGraph` and its `BranchMorphometry` (measured with roots).
+    Fixed nodes: `inlet` (node indices or coordinate triples; default: the roots) at `pressureIn`, every reached end point at
+    ``terminalPressures(pathDistance * metresPerUnit, pressureIn, slope, factor)``.  Resistances: ``branchResistance`` ('HW', `c`,
+    `k`) of the length ``pathLength * metresPerUnit`` and the radius ``meanRadius * voxel * metresPerUnit`` - the distance
+    transform is in voxels and ignores the spacing, so a `spacing` that is not isotropic to 1e-6 relative is a ``ValueError``, not
+    a guess.  Returns ``(FlowResult, extra)``; `extra` holds ``velocity`` (flow / (pi r^2), per branch), ``resistance``,
+    ``fixed``, ``fixedPressure``, ``radius`` and ``length``."""
+    from . import flow as F
+    h = np.asarray(spacing, np.float64).reshape(3)
+    if not (h.max() - h.min()) <= 1e-6 * h.min():
+        raise ValueError('flow needs an isotropic spacing (the radii are in voxels): got {}'.format(h.tolist()))
+    if measured.depthLevel is None:
+        raise ValueError('flow needs a morphometry measured with roots')
+    inlets = measured.roots if inlet is None else _root_indices(inlet, graph.nodeCoords)
+    if not len(inlets):
+        raise ValueError('flow needs at least one inlet')
+    N = int(graph.nodeCoords.shape[0])
+    fixed = (np.asarray(graph.nodeKind) == 0) & (np.asarray(measured.depthLevel) >= 0)
+    distance = np.where(fixed, measured.pathDistance, 0.0)
+    pressure = F.terminalPressures(distance * float(metresPerUnit), pressureIn, slope, factor)
+    fixed[inlets] = True
+    pressure[inlets] = float(pressureIn)
+    length = np.asarray(measured.pathLength, np.float64) * float(metresPerUnit)
+    radius = np.asarray(measured.meanRadius, np.float64) * (float(h[0]) * float(metresPerUnit))
+    R = F.branchResistance(length, radius, law='HW', c=c, k=k)
+    result = F.simulateFlow(graph, R, fixed, pressure, k=k, tol=tol, maxIter=maxIter, device=device)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        velocity = result.flow[0] / (np.pi * radius ** 2)
+    return result, {'velocity': velocity, 'resistance': R, 'fixed': fixed, 'fixedPressure': pressure, 'radius': radius, 'length': length}
+
+
+def _add_simulation_data(graph, result, extra, baseFolder):
+    """``simulationData`` into the entries of ``segmentInfoDict.pkl`` (velocity, flow) and ``nodeInfoDict.pkl`` (pressure), as the
+    reference's updateNetworkWithSimulationResult leaves them; nodes of a component without a fixed node get none."""
+    import pickle
+    for name in (SEGMENT_INFO_FILE, NODE_INFO_FILE):
+        path = os.path.join(baseFolder, name)
+        with open(path, 'rb') as f:
+            info = pickle.load(f)
+        if name == SEGMENT_INFO_FILE:
+            for k, d in info.items():
+                d['simulationData'] = {'velocity': float(extra['velocity'][k]), 'flow': float(result.flow[0, k])}
+        else:
+            for v, c in enumerate(np.asarray(graph.nodeCoords).tolist()):
+                if not np.isnan(result.pressure[0, v]):
+                    info[tuple(c)]['simulationData'] = {'pressure': float(result.pressure[0, v])}
+        with open(path, 'wb') as f:
+            pickle.dump(info, f, protocol=2)
+
+
+def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None, flow=None):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -1083,7 +1139,14 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     `compartmentTerritories` in the affine's spacing) and the territories' ``sizes`` and ``volumes`` into the npz; with
     ``morphometry=True`` the entries of ``segmentInfoDict.pkl`` / ``nodeInfoDict.pkl`` of owned branches and nodes gain
     ``partitionName``, the segments ``segmentLevel``.  The returned values are those of a run without it; without `compartments`
-    every file is what it was."""
+    every file is what it was.
+    With `flow` as well (it needs ``morphometry=True`` and `roots`): a dict of `flowOnGraph`'s arguments - ``pressureIn``, ``slope``,
+    ``c``, and optionally ``k``, ``metresPerUnit`` (default 1e-3: the affine is in millimetres), ``factor``, ``inlet``, ``tol``,
+    ``maxIter``.  ``flowResult.npz`` (the `FlowResult` and `flowOnGraph`'s extras) is written, and the entries of
+    ``segmentInfoDict.pkl`` / ``nodeInfoDict.pkl`` gain ``simulationData`` with ``velocity`` and ``flow`` / ``pressure``.  The
+    returned values are those of a run without it; without `flow` every file is byte for byte what it was."""
+    if flow is not None and (not morphometry or roots is None):
+        raise ValueError('flow needs morphometry=True and roots')
     if compartments is not None and prune is None:
         raise ValueError('compartments needs prune (prune=(0, 0.0) prunes nothing)')
     if morphometry and prune is None:
@@ -1135,6 +1198,12 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
         measured = branchMorphometry(graph, vesselVolumeMask=vesselVolumeMask, spacing=spacing, roots=roots)
         for name in (writeMorphometry(graph, measured, baseFolder) if parts is None else writeMorphometry(graph, measured, baseFolder, parts=parts)):
             print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
+    if flow is not None:
+        from . import flow as _flow
+        solved, extra = flowOnGraph(graph, measured, spacing, **flow)
+        _add_simulation_data(graph, solved, extra, baseFolder)
+        name = _flow.writeFlow(solved, baseFolder, **extra)
+        print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if parts is not None:
         compartmentSizes = None
         if territories:

@@ -60,6 +60,11 @@
  *                      tests/compartment_model.py; bit-identical repeats.  Not claimed: the reference's list order, its
  *                      order-dependent depthLevel and segmentIndexList in loops, voxels of a cluster other than the
  *                      representative, per-compartment flow quantities.
+ *   vmask_flow         the network solve of the reference's fluidSimulation.py (computeNetworkDetail's equations, :4636-4728) as a
+ *                      signed solve: the pressures at the free nodes and the flow in every branch for S scenarios of one graph in
+ *                      one launch; DESIGN.md section 9, f13.  Claimed: at k == 1 bit equality with tests/flow_model.py, iteration
+ *                      counts included; at k != 1 the stated residual and a measured distance to a direct solver; bit-identical
+ *                      repeats.  Not claimed: the reference's optimiser and weights, its distributeFlow mode, pulsatile flow.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -323,6 +328,56 @@ int vmask_compartments(int device, int64_t n0, int64_t n1, int64_t n2,
                        uint8_t* node_comp, int64_t* node_depth, int64_t* node_level,         /* nnode each */
                        uint8_t* branch_comp, int64_t* branch_level,                          /* nbranch each */
                        int64_t* comp_counts /* (ncomp + 1) x 3 */, int64_t* counts /* 2, may be NULL */);
+
+/* The flow solve on the branch graph: S >= 1 scenarios of one topology in one launch.  The graph is vmask_branches': nnode nodes,
+ * nbranch branches with branch_ends[2 nbranch].  A branch with ends -1 -1 (a closed curve) or with both ends on one node (a
+ * loop) carries no flow: Q = 0, it takes no part.  Parallel branches are ordinary.
+ * fixed[nnode] (0 / non-zero, the same for all scenarios); resistance: nbranch values used by every scenario (r_stride 0) or
+ * S x nbranch (r_stride nbranch), R > 0 and finite; fixed_pressure: nnode values (p_stride 0) or S x nnode (p_stride nnode), read at
+ * the fixed nodes only; one exponent k, 1 <= k <= 3.
+ * THE LAW, with Q_b the flow from branch_ends[b][0] = u to branch_ends[b][1] = v and D = P_u - P_v:
+ *   D = R_b |Q_b|^(k-1) Q_b,  that is  Q_b = sign(D) (|D| / R_b)^(1/k) = copysign(pow(fl(|D| / R_b), fl(1 / k)), D);  for k == 1: fl(D / R_b).
+ * THE UNKNOWN: P at the free nodes such that at every free node i the signed sum of the incident flows (s_ib = +1 where i is the
+ * branch's first end, -1 where it is the second) is 0 - unique in every component that holds a fixed node.  A component without
+ * a fixed node is floating: P = NaN (0x7ff8000000000000) at its nodes, Q = 0 in its branches; counts = {floating components,
+ * floating nodes} (may be NULL; an unfixed node without a participating branch is such a component).
+ * node_pressure (S x nnode), branch_flow (S x nbranch): branch_flow is computed from the returned node_pressure by the law, so every
+ * branch satisfies it by construction.  status (S x 3, int64): [0] converged: max over the free nodes |sum_b s_ib Q_b| <= tol
+ * max_b |Q_b|; [1] the outer iterations run; [2] the inner iterations summed.  residual (S): the final max |sum| / max |Q| (0 where
+ * both are 0).  A scenario that does not converge within max_iter outer iterations holds its last iterate and says so in status;
+ * it neither fails the call nor touches another scenario.
+ * THE ITERATION (one workgroup of T = 256 threads per scenario; these choices describe the run, the contract is the residual):
+ *   start   P = its pressure at a fixed node, at a free node the pressure of its anchor - the smallest fixed node of its component.
+ *   outer   step n = 0, 1, ..: with c = fl(1 - fl(1 / k)),
+ *             g_b = fl(1 / R_b) when k == 1 or n == 0 (the linear start), otherwise 1 / ((k R_b) pow(a, k - 1)) with
+ *                   a = max(|Qi_b|, floor), floor = (0.01 tol) max_b |Qi_b| (1 / R_b where a is 0);
+ *             at every free node i over its incidence list:  diag_i = sum g_b,  r_i = rhs_i - sum g_b (P_i - P_other),
+ *                   rhs_i = 0 when k == 1 or n == 0, otherwise 0 - c sum s_ib Qi_b;
+ *             conjugate gradients from the current P with z = r / diag:  p = z, rz = sum r z, then while rz > 1e-16 rz_0 and fewer
+ *                   than 2 F + 64 inner iterations (F free nodes):  Ap_i = sum g_b (p_i - p_other) (p = 0 at fixed nodes),
+ *                   pAp = sum p Ap (stop unless > 0), alpha = rz / pAp, P += alpha p, r -= alpha Ap, z = r / diag, rz' = sum r z,
+ *                   beta = rz' / rz, p = z + beta p;
+ *             Q_b by the law from P (branch_flow); for k != 1 the iteration's own flows Qi_b = Q_b at n == 0, else c Qi_b + g_b D_b;
+ *             the residual above; converged ends the scenario.
+ *           Below the floor the law is replaced by a linear one, which moves a flow by at most the floor: 0.01 tol max |Q|.
+ * THE ORDER OF THE SUMS (every operation one IEEE double operation, nothing contracted into an FMA, no floating-point atomics):
+ *   a sum over a node's incidence list: added to 0.0 in the list's order - the node's participating branches in ascending branch
+ *     index - each term formed as fl(g_b fl(x_i - x_other)), fl(+-Q_b);
+ *   a sum over the free nodes j = 0 .. F - 1 (ascending node id): thread t adds its terms j = t, t + T, .. to 0.0 in sequence; every
+ *     wave of 64 threads then runs a_l <- a_l + a_(l xor s) for s = 32, 16, 8, 4, 2, 1; the four wave sums are added as
+ *     ((w0 + w1) + w2) + w3.  The maxima are order-free.
+ * Repeats are bit-identical, and a scenario's results do not depend on the other scenarios of the call.  For k == 1 no pow runs
+ * and every output is a pure function of the inputs in IEEE arithmetic (tests/flow_model.py restates it); for k != 1 the results
+ * depend on the device's pow.
+ * VRG_E_ARG, before anything is written: nscen < 1; k outside [1, 3]; tol not in (0, 1); max_iter < 1; a stride that is neither 0
+ * nor the row length; a negative count, nbranch >= 2^30; and, counted on the device: an end that is no node id or -1 -1, an R of a
+ * participating branch that is not finite and > 0, a fixed pressure that is not finite.  VRG_E_MEM: the tables where they are host
+ * arrays, the outputs likewise, 13 bytes per node and 9 per branch for the topology and, per scenario, 32 bytes per node and 16
+ * per branch of work space do not fit the device; everything allocated is freed. */
+int vmask_flow(int device, int64_t nnode, int64_t nbranch, const int64_t* branch_ends, const uint8_t* fixed,
+               int64_t nscen, const double* resistance, int64_t r_stride, const double* fixed_pressure, int64_t p_stride,
+               double k, double tol, int64_t max_iter,
+               double* node_pressure, double* branch_flow, int64_t* status, double* residual, int64_t* counts /* 2, may be NULL */);
 
 const char* vmask_last_error(void);
 
