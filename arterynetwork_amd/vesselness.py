@@ -106,14 +106,15 @@ def vesselnessFilter(volume, sigmas, alpha=0.5, beta=0.5, gamma=None, brainVolum
     return out
 
 
-def main(baseFolder=None, sigmas=(0.5, 1.0, 1.5, 2.0), alpha=0.5, beta=0.5, gamma=None, bright=True):
-    """File-level step in front of ``generateVesselVolume.main``: the vesselness of ``brainVolume.nii.gz`` - inside
+def main(baseFolder=None, sigmas=(0.5, 1.0, 1.5, 2.0), alpha=0.5, beta=0.5, gamma=None, bright=True, volumeName=BRAIN_FILE):
+    """File-level step in front of ``generateVesselVolume.main``: the vesselness of ``brainVolume.nii.gz`` (or `volumeName`,
+    ``denoise.main``'s output for one) - inside
     ``brainVolumeMask.nii.gz`` when that file exists - written as float32 ``vesselnessFiltered.nii.gz`` with the input's
     affine into the same folder; `sigmas` in the units of the affine (millimetres), the voxel spacing being the norms of the
     affine's columns.  Returns the float64 volume."""
     if baseFolder is None:
         baseFolder = os.getcwd()
-    volume, affine = loadVolume(baseFolder, BRAIN_FILE)
+    volume, affine = loadVolume(baseFolder, volumeName)
     mask = None
     if os.path.exists(os.path.join(baseFolder, BRAIN_MASK_FILE)):
         mask, _ = loadVolume(baseFolder, BRAIN_MASK_FILE)

@@ -1,6 +1,6 @@
 /*
  * vmask.h - C-ABI (in libvrg_hip.so) of the voxel passes on either side of the VRG stage
- * (DESIGN.md section 9 rows f5-f11): what Code/generateVesselVolume.py and its consumers do with
+ * (DESIGN.md section 9 rows f5-f14): what Code/generateVesselVolume.py and its consumers do with
  * scipy / scikit-image on the CPU, as HIP kernels on MI355X.
  *
  *   vmask_edt          scipy.ndimage.distance_transform_edt(mask)       generateVesselVolume.py:183,
@@ -65,6 +65,15 @@
  *                      one launch; DESIGN.md section 9, f13.  Claimed: at k == 1 bit equality with tests/flow_model.py, iteration
  *                      counts included; at k != 1 the stated residual and a measured distance to a direct solver; bit-identical
  *                      repeats.  Not claimed: the reference's optimiser and weights, its distributeFlow mode, pulsatile flow.
+ *   vmask_diffuse      the "MR image denoising" step that the reference's README (Pre-processing) leaves to an external GUI tool, in
+ *                      front of vmask_vesselness: explicit Perona-Malik diffusion over the 6 neighbours in float64 by the
+ *                      definition below; DESIGN.md section 9, f14.  Claimed: with the rational conductance bit equality with
+ *                      the numpy restatement tests/denoise_model.py, with the exponential one agreement to 1e-9 of the input's
+ *                      span (the device's exp); bit-identical repeats.  Not claimed: agreement with the external tool's
+ *                      filters (their discretisation differs and they rescale K every step), an automatic K.
+ *   vmask_median       the median over a window of at most 3 x 3 x 3 voxels, scipy.ndimage.median_filter(mode='nearest'); it
+ *                      keeps the value set of integer data.  Claimed: equality with scipy as numbers.  Not claimed: wider
+ *                      windows.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -378,6 +387,40 @@ int vmask_flow(int device, int64_t nnode, int64_t nbranch, const int64_t* branch
                int64_t nscen, const double* resistance, int64_t r_stride, const double* fixed_pressure, int64_t p_stride,
                double k, double tol, int64_t max_iter,
                double* node_pressure, double* branch_flow, int64_t* status, double* residual, int64_t* counts /* 2, may be NULL */);
+
+/* Perona-Malik diffusion of a 3-D volume I (VRG_F32 or VRG_F64, assumed finite; float32 is an input type only): `iterations`
+ * explicit steps over the 6 neighbours, float64 throughout.
+ * The host forms, in double, ih_a = 1.0 / h_a per axis (spacing == NULL: 1 1 1) and iK = 1.0 / K.  u^0 = (double) I.
+ * One step at voxel p: acc = 0.0; the neighbours q in the order axis 0 -, axis 0 +, axis 1 -, axis 1 +, axis 2 -, axis 2 +, the
+ * neighbour's index clamped at the faces (a missing neighbour is p itself: d = 0); per neighbour on axis a
+ *     d = u[q] - u[p];  g = d * ih_a;  t = g * iK;
+ *     c = 1.0 / (1.0 + t * t)      function 0, "rational"
+ *     c = exp(-(t * t))            function 1, "exponential"
+ *     acc = acc + (c * g) * ih_a;
+ * then u'[p] = u[p] + dt * acc.  EVERY OPERATION IS ONE IEEE DOUBLE OPERATION IN EXACTLY THIS ASSOCIATION, nothing contracted
+ * into an FMA.  out (float64) is u after `iterations` steps; it must not overlap the input, which is never written.
+ * Stability: B = 1.0 / (2.0 * ((ih_0 * ih_0 + ih_1 * ih_1) + ih_2 * ih_2)), 1/6 at unit spacing.  time_step <= 0 is automatic:
+ * dt = 0.5 * B.  For dt <= B a step is a convex combination of the voxel and its neighbours: nothing leaves the input's range
+ * and a constant volume is a fixed point to the last bit.
+ * With function 0 the result is a pure function of the inputs in IEEE arithmetic (tests/denoise_model.py restates it); with
+ * function 1 it depends on the device's exp.  Repeats are bit-identical.
+ * One launch per step, ping-pong between out and one float64 work volume - the only allocation of a call with device pointers.
+ * VRG_E_ARG, before anything is written: iterations outside 1..1000; K not finite and positive; a spacing not finite and
+ * positive; time_step not finite or above B; function not 0 or 1; a dtype other than the two; a null pointer; a shape outside
+ * the envelope of the other passes.  VRG_E_MEM: the input, the output and one float64 volume do not fit the device (volumes are
+ * not processed in slabs); everything allocated is freed. */
+int vmask_diffuse(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
+                  double K, int iterations, double time_step, int function, double* out);
+
+/* Median over the window of (2 r0 + 1) x (2 r1 + 1) x (2 r2 + 1) voxels around every voxel, every radius 0 or 1, the window's
+ * indices clamped at the faces: scipy.ndimage.median_filter(I, size=(2 r0 + 1, 2 r1 + 1, 2 r2 + 1), mode='nearest').  A window
+ * has 1, 3, 9 or 27 values, so the median is one of the input's values: exact in either type, and the output's value set is a
+ * subset of the input's.  volume: VRG_F32 or VRG_F64, assumed finite; out: the same type, not overlapping the input, which is
+ * never written.  Radii (1, 1, 0) give the in-plane 3 x 3 median of a thick-slice volume; (0, 0, 0) is a copy.  Equal as
+ * numbers: where -0.0 and +0.0 meet in a window either may come back.
+ * VRG_E_ARG, before anything is written: a radius outside {0, 1}; a dtype other than the two; a null pointer; a shape outside
+ * the envelope of the other passes.  VRG_E_MEM: the input and the output do not fit the device; everything allocated is freed. */
+int vmask_median(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, int r0, int r1, int r2, void* out);
 
 const char* vmask_last_error(void);
 
