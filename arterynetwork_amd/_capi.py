@@ -303,8 +303,8 @@ class Session:
 
     def stats(self):
         """Diagnostics: how often a trip was handed back to the host and why, array capacities."""
-        a = (C.c_int64 * 26)()
-        self._check(self.lib.get_stats(self._h, a, 26))
+        a = (C.c_int64 * 28)()
+        self._check(self.lib.get_stats(self._h, a, 28))
         if a[14]:
             dense_kernel = 'k_recount_pipe<3,{}>'.format('true' if a[9] else 'false')
         else:
@@ -317,6 +317,8 @@ class Session:
                 # mode, the decision of the last vrg_init (None where the option decided)
                 'dense_storage': {0: 'fp32 (4 B/voxel)', 1: 'u16 level index (2 B/voxel)', 2: 'float64 (8 B/voxel)', 3: 'u16 level index (2 B/voxel)'}.get(a[10]),
                 'storage16_option': a[23], 'storage16_auto': None if a[24] < 0 else bool(a[24]), 'level_index_builds': a[25],
+                # option dense_memo (16-bit storage): bytes of the per-group intensity sums, and the all-outer groups of the pass dense_bytes describes
+                'dense_memo_bytes': a[26], 'dense_memo_groups': a[27],
                 'dense_nt_loads': bool(a[9]), 'dense_workgroups': a[11], 'dense_listed_units': a[13]}
 
     def nlevels(self):

@@ -20,7 +20,9 @@
 //     k_recount_pipe / k_recount_bits : the dense kernel (every listed 1024-voxel unit, HBM-bound, read-only: 4 B intensity - or a 2-B
 //        level index - of included voxels + 2 class bits per voxel): region sizes and intensity sums (:113-116, :249-250), reduced by its
 //        last workgroup, checked against the sizes the band side keeps by increments.  k_recount_pipe (fp32 storage) walks the list two
-//        trips deep; 16-bit storage stays one trip deep in k_recount_bits (two deep measured slower: profiles/depth16_ab_880.json)
+//        trips deep; 16-bit storage stays one trip deep in k_recount_bits (two deep measured slower: profiles/depth16_ab_880.json) and, on
+//        large volumes (option dense_memo), takes the intensity sum of a 256-voxel group whose voxels are all outer from a table built
+//        once per volume (VrgBackend::gsum) instead of fetching the group
 //     -> on several GPUs: slab all-reduce -> k_dense_fin (the same check on the totals, trace sums).
 //   Stream A does not join: it runs up to two sweeps ahead of the dense pass (two copies of the class bits).
 // Labels are updated IN PLACE: measured on MI355X, streaming I + labels read-only runs at 5.8-6.0 TB/s
@@ -79,6 +81,10 @@ struct VrgBackend {
     int nt_loads = -1;                                // option "nt_loads": -1 = by the size of the pass, 0 / 1 = ordinary / non-temporal loads
     int verify_every = 1;                             // option "verify_every": the dense pass on every n-th sweep only (0: never)
     int dense_pipe = 1;                               // option "dense_pipe": fp32 storage + skip_excluded run the two-trips-deep recount (k_recount_pipe)
+    int dense_memo = -1;                              // option "dense_memo": 16-bit storage + skip_excluded take the sums of all-outer 256-voxel groups from gsum (-1: large volumes only, 1: always, 0: never)
+    double* gsum = nullptr; size_t gsum_bytes = 0;    // sum of the values of every 256-voxel group of the padded volume (k_build_gsum), built with the level indices ...
+    const uint16_t* gsum_for = nullptr;               // ... at this address (be_build_lev16); freed with them (be_free) or with the backend
+    long long memo_groups = 0;                        // full groups be_dense_bytes counted last (stats: dense_memo_groups)
     uint64_t pass_bytes = 0;                          // bytes a dense pass fetches, counted at the end of init (0: not known yet)
     uint32_t memo_above = 32768;                      // option "memo_above": band entries above which a fused trip keeps the per-level memo (k_memo)
     long long memo_trips = 0;                         // fused trips that did

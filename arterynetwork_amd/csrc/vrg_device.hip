@@ -156,6 +156,17 @@ __device__ __forceinline__ void stats_group_outer(SweepAcc& a, uint32_t wj, cons
         }
     }
 }
+// ... and for the table of doubles with one entry more, s_dv[lz] = +0.0 (the memoising pass, MODE 3): the INDEX is selected before the
+// look-up - a voxel that is not outer reads entry lz - instead of the 64-bit value after it: one v_cndmask_b32 per voxel instead of
+// two; the same +0.0 is added in the same place, so the sums are bit-identical.  (Measured at 880x880x640, three rounds in turn,
+// 1024 workgroups: dense 0.1076-0.1079 -> 0.1027-0.1029 ms; profiles/dense_memo_ab_880.json.)
+__device__ __forceinline__ void stats_group_outer_idx(SweepAcc& a, uint32_t wj, const UnitVals<3>& u, int j, const float* s_val, uint32_t lz) {
+    const double* s_dv = reinterpret_cast<const double*>(s_val);
+    a.sout += s_dv[(wj & 2u) ? (u.q[j].x & 0xffffu) : lz];
+    a.sout += s_dv[(wj & 8u) ? (u.q[j].x >> 16) : lz];
+    a.sout += s_dv[(wj & 32u) ? (u.q[j].y & 0xffffu) : lz];
+    a.sout += s_dv[(wj & 128u) ? (u.q[j].y >> 16) : lz];
+}
 // SKIP: a group of four voxels per lane whose 256 voxels are all excluded costs the wave nothing (the branch is
 // wave-uniform there); partly excluded groups run with the excluded lanes masked off.  Adding +0.0 or not adding at
 // all gives the same sums (the accumulators never hold -0.0: they start at +0.0).
@@ -169,12 +180,17 @@ __device__ __forceinline__ double unit_value(const UnitVals<MODE>& u, int j, int
 // Most groups inside the brain mask hold four outer voxels (class byte 0xAA): when every lane that takes part has
 // such a group, the four values go straight into the outer sum - the same additions in the same order as the general
 // path makes (which also adds +0.0 to the inner sum four times: no change).
-template <int MODE, bool SKIP>
-__device__ __forceinline__ void stats_bits(SweepAcc& a, uint32_t w, const UnitVals<MODE>& u, const float* s_val) {
+// MEMO (option dense_memo, 16-bit storage): a group whose 256 voxels are all outer - class byte 0xAA in every lane, bit j of the
+// wave-uniform mask fm - adds the sum of its values, built once per volume (k_build_gsum, vrg_init.hip: its intensities never
+// change), to the wave's accumulator of such sums instead: no index load, no look-up.  Every other group goes the paths below.
+struct UnitSums { double g[4]; };
+template <int MODE, bool SKIP, bool MEMO = false>
+__device__ __forceinline__ void stats_bits(SweepAcc& a, uint32_t w, const UnitVals<MODE>& u, const float* s_val, uint32_t fm = 0u, const UnitSums* gs = nullptr, double* gacc = nullptr, uint32_t lz = 0u) {
     a.nin += __popc(w & 0x55555555u); a.nout += __popc(w & 0xAAAAAAAAu);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const uint32_t wj = (w >> (8 * j)) & 0xffu;
+        if constexpr (MEMO) { if ((fm >> j) & 1u) { *gacc += gs->g[j]; continue; } }
         if (!SKIP || wj != 0u) {
             if (SKIP && __builtin_amdgcn_ballot_w64(wj != 0xAAu) == 0ull) {
                 float lv[4]; double dv[4];
@@ -184,12 +200,28 @@ __device__ __forceinline__ void stats_bits(SweepAcc& a, uint32_t w, const UnitVa
             } else if (SKIP && __builtin_amdgcn_ballot_w64((wj & 0x55u) != 0u) == 0ull) {
                 // no lane holds an inner voxel here (the rim of the brain mask: outer and excluded voxels mixed): the outer
                 // sum alone, masked - the general path would add +0.0 to the inner sum sixteen times for nothing
-                stats_group_outer<MODE>(a, wj, u, j, s_val);
+                if constexpr (MEMO && MODE == 3) stats_group_outer_idx(a, wj, u, j, s_val, lz);
+                else stats_group_outer<MODE>(a, wj, u, j, s_val);
             } else {
                 stats_group<MODE>(a, wj, u, j, s_val);
             }
         }
     }
+}
+// the full groups of a unit's class word (all 64 lanes take part: the walk's loop is wave-uniform)
+__device__ __forceinline__ uint32_t full_groups(uint32_t w) {
+    const uint32_t x = w ^ 0xAAAAAAAAu;
+    uint32_t m = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; j++) if (__builtin_amdgcn_ballot_w64((x & (0xffu << (8 * j))) != 0u) == 0ull) m |= 1u << j;
+    return m;
+}
+// the four group sums of unit u, as scalar loads like the list entries (written by an earlier kernel only: constant address space)
+__device__ __forceinline__ void load_gsum(const double* gsum, uint32_t u, UnitSums& o) {
+    typedef const double __attribute__((address_space(4))) cf64;
+    const cf64* p = (cf64*)gsum + ((size_t)u << 2);
+#pragma unroll
+    for (int j = 0; j < 4; j++) o.g[j] = p[j];
 }
 // An entry of the unit list as a scalar load: through a pointer into the constant address space, which tells the compiler that
 // nothing in this kernel writes the list (k_gate, the kernel before it on the stream, does) - behind the workgroup barrier that
@@ -209,11 +241,11 @@ __device__ __forceinline__ uint32_t load_cls(const uint32_t* cls, uint32_t u, ui
 // consecutive voxels are excluded (the brain mask leaves long runs).  The sums are bit-identical: a class-0 voxel
 // contributes +0.0 either way.
 template <int MODE, bool NT, bool SKIP>
-__device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t lane, uint32_t w, UnitVals<MODE>& o) {
+__device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t lane, uint32_t w, UnitVals<MODE>& o, uint32_t fm = 0u) {
     const uint32_t base = (u << 10) + (lane << 2);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const bool need = !SKIP || ((w >> (8 * j)) & 0xffu) != 0u;
+        const bool need = (!SKIP || ((w >> (8 * j)) & 0xffu) != 0u) && !((fm >> j) & 1u);     // (fm: the full groups of a memoising pass - none otherwise)
         if constexpr (MODE == 1 || MODE == 3) {
             o.q[j] = u2v{0u, 0u};
             if (need) { const u2v* pq = reinterpret_cast<const u2v*>(c.lev16 + base + (j << 8)); o.q[j] = NT ? __builtin_nontemporal_load(pq) : *pq; }
@@ -240,8 +272,13 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // makes the same additions in the same order, a class-0 voxel adding +0.0: bit-identical sums - and the units that are
 // not listed are streamed afterwards for their bytes only.
 // The list entries are read through the scalar cache (ulist_entry).
-template <int UNITS, bool NT, int MODE, bool SKIP>
-__global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) {
+// MEMO (16-bit storage with SKIP, option dense_memo): gsum holds the sum of every 256-voxel group's values (four per unit); a
+// unit's four sums arrive through the scalar cache with its class words, one trip ahead, and the groups that are full this
+// sweep take theirs (stats_bits).  The wave adds them in the order it meets them, into an accumulator of their own that
+// joins lane 0's outer sum behind the walk: a fixed order for a given grid, like every other sum of the pass.  The units
+// the slab's faces cut are counted voxel by voxel as ever.
+template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false>
+__global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum) {
     VRG_CHAOS_POINT(7);
     if (check_done && check_done < 3 && !c.dctl[VD_GO]) return;     // the gate says: no sweep to count (the run has stopped) or this sweep's pass is left out
     extern __shared__ __attribute__((aligned(16))) float s_val[];   // 16-bit storage: the level values (c.L floats - MODE 3: doubles -, sized at launch)
@@ -262,6 +299,7 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) 
     if (MODE == 3) {                                 // (the stored value is the float: the same doubles as MODE 1 adds)
         double* s_dv = reinterpret_cast<double*>(s_val);
         for (uint32_t k = threadIdx.x; k < c.L; k += TPB) s_dv[k] = (double)(float)c.lev[k];
+        if (MEMO && threadIdx.x == 0) s_dv[c.L] = 0.0;             // (stats_group_outer_idx)
         __syncthreads();
     }
     const uint32_t* __restrict__ cls = c.clsb[(vrg_load_i64(&c.dctl[VD_RSEQ]) + (check_done >= 3 ? 0 : 1)) & 1];   // (3: the run's last sweep, counted after all)
@@ -271,6 +309,12 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) 
     uint32_t f_lo = (uint32_t)(((uint64_t)lo + 1023u) >> 10), f_hi = hi >> 10;       // units wholly inside it
     if (f_hi < f_lo) f_hi = f_lo;
     SweepAcc acc = {0, 0, 0.0, 0.0};
+    double gacc = 0.0;
+    UnitSums gs[UNITS];
+    if constexpr (MEMO) {
+#pragma unroll
+        for (int q = 0; q < UNITS; q++) load_gsum(gsum, uu[q], gs[q]);
+    }
     // the class words of a trip are fetched one trip ahead (the intensity loads depend on them), before this trip's
     // intensities: loads return in order, so they cost no wait of their own
     uint32_t w[UNITS];
@@ -286,14 +330,28 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done) 
 #pragma unroll
         for (int q = 0; q < UNITS; q++) if (in + q >= n) wn[q] = 0u;          // (uniform: slots past the list's end hold nothing)
         UnitVals<MODE> f[UNITS];
+        if constexpr (MEMO) {
+            UnitSums gn[UNITS];
+            uint32_t fm[UNITS];
 #pragma unroll
-        for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, w[q], f[q]);
+            for (int q = 0; q < UNITS; q++) { load_gsum(gsum, un[q], gn[q]); fm[q] = full_groups(w[q]); }
 #pragma unroll
-        for (int q = 0; q < UNITS; q++) stats_bits<MODE, SKIP>(acc, w[q], f[q], s_val);
+            for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, w[q], f[q], fm[q]);
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) stats_bits<MODE, SKIP, true>(acc, w[q], f[q], s_val, fm[q], &gs[q], &gacc, c.L);
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) gs[q] = gn[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, w[q], f[q]);
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) stats_bits<MODE, SKIP>(acc, w[q], f[q], s_val);
+        }
 #pragma unroll
         for (int q = 0; q < UNITS; q++) { w[q] = wn[q]; uu[q] = un[q]; }
         i = in;
     }
+    if constexpr (MEMO) { if (lane == 0u) acc.sout += gacc; }
     if (!SKIP) {                                               // the bytes of the units that are not listed (they add nothing)
         for (uint32_t u = f_lo + wave; u < f_hi; u += nwaves) {
             if ((c.ubits[u >> 5] >> (u & 31u)) & 1u) continue;
@@ -432,8 +490,9 @@ __global__ void k_cls_build(VrgCtx c) {
 
 // Bytes one dense pass requests from memory for the class copy the last pass read: per listed unit its list entry (4 B)
 // and its class words (256 B; the units the slab's faces cut: always) + every 128-byte intensity line that holds an
-// included voxel (what k_recount_bits<.., SKIP> fetches).
-__global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long long* out) {
+// included voxel (what k_recount_bits<.., SKIP> fetches).  memo (a memoising pass, option dense_memo): a whole unit costs the 32 B
+// of its four group sums more, and a full group of a whole unit - 256 outer voxels - no intensity lines; out[1] counts those groups.
+__global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long long* out, int memo) {
     const uint32_t* __restrict__ cls = c.clsb[vrg_load_i64(&c.dctl[VD_RSEQ]) & 1];
     const uint32_t plane = (uint32_t)c.PY * (uint32_t)c.PX;
     const uint32_t lo = (2u + (uint32_t)c.z0) * plane, hi = (2u + (uint32_t)c.z1) * plane;
@@ -443,20 +502,23 @@ __global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long lon
     const uint32_t lpl = c.lev16 ? 16u : (c.I ? 8u : 4u);          // lanes (of 4 voxels each) per 128-byte line
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-    unsigned long long bytes = 0;
+    unsigned long long bytes = 0, full = 0;
     for (uint32_t u = e0 + wave; u <= e1; u += nwaves) {
         const bool whole = u >= f_lo && u < f_hi;
         if (whole && !((c.ubits[u >> 5] >> (u & 31u)) & 1u)) continue;
         uint32_t w = cls[((size_t)u << 6) + lane];
-        bytes += whole ? 260u : 256u;                               // class words (+ the unit's list entry)
+        bytes += whole ? (memo ? 292u : 260u) : 256u;               // class words (+ the unit's list entry, + its group sums)
         for (int j = 0; j < 4; j++) {
             const uint32_t v = (u << 10) + (j << 8) + (lane << 2);
-            const bool need = v >= lo && v < hi && ((w >> (8 * j)) & 0xffu) != 0u;
+            const uint32_t wj = (w >> (8 * j)) & 0xffu;
+            if (memo && whole && __ballot(wj != 0xAAu) == 0ull) { full++; continue; }    // (wave-uniform)
+            const bool need = v >= lo && v < hi && wj != 0u;
             const uint64_t m = __ballot(need);
             for (uint32_t g = 0; g < 64u; g += lpl) bytes += ((m >> g) & ((1ull << lpl) - 1ull)) ? 128u : 0u;
         }
     }
     if (lane == 0 && bytes) atomicAdd(out, bytes);
+    if (lane == 0 && full) atomicAdd(out + 1, full);
 }
 
 __global__ void k_dense_pack(VrgCtx c) { vrg_dense_pack(c); }
@@ -466,10 +528,24 @@ __global__ void k_dense_fin(VrgCtx c) { vrg_dense_fin_staged(c); }
 // to a little more than the 256-MiB Infinity Cache, ordinary loads keep most of the slab there from sweep to sweep
 // (512x512x170, 102 MB: 0.0345 -> 0.0306 ms per pass, and less HBM traffic for the band kernels to queue behind; 274 MB:
 // 0.0582 -> 0.0545); a larger pass would only thrash the cache (342 MB: even; 548 MB: 0.102 -> 0.112; 1.1 GB: 0.19 -> 0.204).
+// (The memoising 16-bit pass at 880x880x640 requests 362 MB: ordinary loads 0.0969, 0.0984 ms, step 0.104, 0.107; non-temporal
+// 0.0943, 0.0947, step 0.097 - the line stays where it is.)
 constexpr uint64_t NT_ABOVE_BYTES = 300ull << 20;
 bool dense_nt(const VrgBackend* b, const VrgCtx&) {
     if (b->nt_loads >= 0) return b->nt_loads != 0;
     return b->pass_bytes == 0 || b->pass_bytes > NT_ABOVE_BYTES;
+}
+
+// Memoised group sums (option dense_memo): 16-bit storage with skip_excluded, and the sums on hand are those of the level indices
+// this pass reads (be_build_lev16 builds both; the pair is dropped together).  By default (-1) only a volume of more than 100 000
+// units memoises: the pass of a small one comes out of the Infinity Cache and is not what bounds the step, so the bytes it saves buy
+// nothing, and it measured slower (512x512x170, 46 000 units, one run each: pass 0.0261 -> 0.0280 ms, step 0.0332 -> 0.0347;
+// 880x880x640: 0.117 -> 0.095, 1024^3: 0.224 -> 0.170).  The whole volume decides, not the slab, so that the ranks of a group
+// decide alike (as for the automatic 16-bit storage itself); the slab passes of a large volume have not been timed with it.
+// 1: every 16-bit pass; 0: none.
+bool dense_memo(const VrgBackend* b, const VrgCtx& c) {
+    if (!b->dense_memo || !b->skip || !c.lev16 || !b->gsum || b->gsum_for != c.lev16) return false;
+    return b->dense_memo > 0 || ((uint64_t)c.PV >> 10) > 100000;
 }
 
 // workgroups of the dense recount: >= 32 one-KiB units per wave, at most 1 workgroup per CU
@@ -488,7 +564,11 @@ int dense_blocks(const VrgBackend* b, const VrgCtx& c) {
     // 1280 -> 0.116 / 0.224, 1536 -> 0.126 / 0.245, 1792 -> 0.117 / - ms; with vector loads of the entries 1536 was best: 0.122 / 0.240)
     // (small passes, where the band chain bounds the step: 512x512x170 942 -> 0.0428 ms/step, 384-512 -> 0.0381; 80-plane slab
     // 1289 -> 0.0516, 512 -> 0.0394; 160 planes 1536 -> 0.0633, 1024 -> 0.0499 - measured with vector loads of the entries)
-    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS, std::max<uint64_t>(64, units / 48));
+    // The memoising pass (dense_memo) does half the work per trip - the full groups cost it neither loads nor look-ups - and wants more waves
+    // to cover what a trip still waits for: six workgroups per CU (tools/sweep_recount.py --storage16, 60 sweeps per point, one process per shape,
+    // 880x880x640 / 1024^3: 768 -> 0.120 / 0.237, 1024 -> 0.107, 0.107 / 0.204, 0.204, 1280 -> 0.098, 0.099 / 0.188, 1536 -> 0.097, 0.100 / 0.180, 0.181,
+    // 1792 -> 0.107, 0.108 / 0.199, 0.206, 2048 -> 0.104 / - ms; before the rim path of stats_group_outer_idx).  Small passes keep their grid.
+    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (dense_memo(b, c) ? 6 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
     // fp32: whole or half multiples of the CU count only - 552 or 640 workgroups leave some CUs with a wave more than others for
     // the whole pass (880x880x160: 552 -> 0.058 ms, 384 -> 0.050; 880x880x320: 640 -> 0.103, 512 -> 0.094, 768 -> 0.091 but a
     // slower step, 0.1035 vs 0.1003, the band chain queueing behind three waves per SIMD); one session, tools/gpu_slabsweep.sh
@@ -555,14 +635,20 @@ static bool dense_deep(const VrgBackend* b, const VrgCtx& c) { return b->dense_p
 // The start / stop events ride on the dispatch itself (hipExtLaunchKernel): no separate event packets in the stream,
 // which cost ~4 us each between two back-to-back recounts.
 template <bool NT, bool SKIP>
-static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, const double* gsum, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+    const double* const none = nullptr;
     if constexpr (SKIP) {
         if (deep) { hipExtLaunchKernelGGL((k_recount_pipe<3, NT>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check); return; }
+        if (gsum) {            // (dense_memo: 16-bit storage)
+            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum);
+            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum);
+            return;
+        }
     }
-    if (c.lev16 && c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(double), st, e_start, e_stop, 0, c, check);
-    else if (c.lev16) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check);
-    else if (c.I) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 0, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check);
-    else hipExtLaunchKernelGGL((k_recount_bits<2, NT, 2, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check);
+    if (c.lev16 && c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(double), st, e_start, e_stop, 0, c, check, none);
+    else if (c.lev16) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, none);
+    else if (c.I) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 0, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none);
+    else hipExtLaunchKernelGGL((k_recount_bits<2, NT, 2, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none);
 }
 // One dense pass of this handle on stream st: the gate in front of a sweep's pass (checks 1 and 2: it waits, on the device, until the
 // sweep's labels are in place, and keeps the unit list current; also when every pass is counted - with several verifiers this handle
@@ -574,8 +660,9 @@ static void launch_recount(VrgBackend* b, const VrgCtx& c, int check, hipStream_
     const int blocks = dense_blocks(b, c);
     const bool nt = dense_nt(b, c), deep = dense_deep(b, c) && check != 0 && check != 3;
     if (check == 1 || check == 2) k_gate<<<1, GATE_THREADS, 0, st>>>(c, b->verify_every, check);
-    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, st, e_start, e_stop); }
-    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, st, e_start, e_stop); }
+    const double* const gsum = dense_memo(b, c) ? b->gsum : nullptr;
+    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, gsum, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, gsum, st, e_start, e_stop); }
+    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, nullptr, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, nullptr, st, e_start, e_stop); }
 }
 
 // init: the class bits and the unit list from the labels, then the first count (the sizes the sweeps keep by increments start from it)
@@ -638,19 +725,23 @@ void be_dense_info(VrgBackend* b, const VrgCtx& c, int64_t out[5]) {
 }
 uint64_t be_dense_bytes(VrgBackend* b, const VrgCtx& c) {
     use_device(b);
+    b->memo_groups = 0;
     if (!b->skip) {            // every voxel of the slab's units is streamed
         const uint64_t plane = (uint64_t)c.PY * c.PX, lo = (2u + (uint64_t)c.z0) * plane, hi = (2u + (uint64_t)c.z1) * plane;
         const uint64_t bpv4 = c.lev16 ? 9 : (c.I ? 17 : 33);      // 4 x (intensity bytes + 0.25)
         return (hi - lo) * bpv4 / 4;
     }
     HIP_CHECK(hipStreamSynchronize(b->sb));
-    unsigned long long* d = nullptr; unsigned long long v = 0;
-    HIP_CHECK(hipMalloc(&d, 8));
+    unsigned long long* d = nullptr; unsigned long long v[2] = {0, 0};
+    HIP_CHECK(hipMalloc(&d, 16));
     if (!d) return 0;
-    HIP_CHECK(hipMemsetAsync(d, 0, 8, b->sa));
-    k_dense_bytes<<<ITEM_BLOCKS, TPB, 0, b->sa>>>(c, d);
-    HIP_CHECK(hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, b->sa));
+    HIP_CHECK(hipMemsetAsync(d, 0, 16, b->sa));
+    k_dense_bytes<<<ITEM_BLOCKS, TPB, 0, b->sa>>>(c, d, dense_memo(b, c) ? 1 : 0);
+    HIP_CHECK(hipMemcpyAsync(v, d, 16, hipMemcpyDeviceToHost, b->sa));
     HIP_CHECK(hipStreamSynchronize(b->sa));
     HIP_CHECK(hipFree(d));
-    return v;
+    b->memo_groups = (long long)v[1];
+    return v[0];
 }
+// the memoised group sums of this handle: {bytes held, full groups be_dense_bytes last counted}
+void be_dense_memo_info(VrgBackend* b, const VrgCtx&, int64_t out[2]) { out[0] = b->gsum ? (int64_t)b->gsum_bytes : 0; out[1] = b->memo_groups; }

@@ -14,6 +14,10 @@
 #include "vrg_backend.h"
 #include "vrg_items.h"
 
+// An extension only the device backend has (vrg_device.hip; null where the engine is linked with a backend that lacks it): its memoised
+// group sums of the 16-bit dense pass - out[0] = bytes held, out[1] = all-outer groups counted by the last be_dense_bytes.
+__attribute__((weak)) void be_dense_memo_info(VrgBackend* b, const VrgCtx& c, int64_t out[2]);
+
 #ifndef VRG_API_PREFIX
 #define VRG_API_PREFIX vrg_
 #endif
@@ -381,7 +385,7 @@ int API(set_option)(vrg_handle* h, const char* name, int64_t value) {
     else if (n == "bin_above") { if (value < 0) return fail(h, VRG_E_ARG, "bin_above: a number of levels >= 0"); h->bin_above = value; h->inited = false; }
     else if (n == "verify_every") { if (value < 0) return fail(h, VRG_E_ARG, "verify_every: 0 (never), 1 (every sweep: the default) or n > 1 (every n-th sweep)"); h->verify_every = (int)std::min<int64_t>(value, 1 << 20); be_set_tuning(h->be, name, value); }
     else if (n == "open_sweeps" || n == "mark_compact" || n == "band_blocks_max") be_set_tuning(h->be, name, value);
-    else if (n == "sweep_blocks" || n == "prio_mode" || n == "small_flips" || n == "fuse_max" || n == "memo_above" || n == "serial_streams" || n == "skip_excluded" || n == "nt_loads" || n == "dense_pipe") be_set_tuning(h->be, name, value);
+    else if (n == "sweep_blocks" || n == "prio_mode" || n == "small_flips" || n == "fuse_max" || n == "memo_above" || n == "serial_streams" || n == "skip_excluded" || n == "nt_loads" || n == "dense_pipe" || n == "dense_memo") be_set_tuning(h->be, name, value);
     else if (n == "storage16") h->storage16 = value < 0 ? -1 : (value != 0);      // takes effect at the next vrg_init
     else if (n == "narrow_alloc_fault") h->narrow_alloc_fault = value != 0;   // tests: the 2 B/voxel buffer cannot be allocated (automatic mode keeps the stored type; storage16 = 1 fails)
     else if (n == "narrow_above") { if (value < 0) return fail(h, VRG_E_ARG, "narrow_above: a number of bytes >= 0"); h->narrow_above = value; }   // ... as does this
@@ -833,7 +837,8 @@ int API(get_levels)(vrg_handle* h, double* values, int32_t* hin, int32_t* hout, 
 // out[5] = pool capacity, out[6] = marked-list capacity, out[7] = pool slots in use; with cap >= 9 also
 // out[8] = bytes one dense pass requests from memory with the current labels (0 before init); with cap >= 14 also how the
 // dense pass is launched: out[9] = non-temporal loads, out[10] = storage (0 fp32, 1 u16 level index, 2 f64), out[11] =
-// workgroups, out[12] = skip_excluded, out[13] = listed units
+// workgroups, out[12] = skip_excluded, out[13] = listed units; with cap >= 28 out[26] = bytes of the dense pass's memoised group sums,
+// out[27] = all-outer groups of the pass out[8] describes
 int API(get_stats)(vrg_handle* h, int64_t* outp, int64_t cap) {
     if (!h || !outp || cap < 8) return VRG_E_ARG;
     for (int i = 0; i < 4; i++) outp[i] = h->bails[i];
@@ -862,6 +867,11 @@ int API(get_stats)(vrg_handle* h, int64_t* outp, int64_t cap) {
     }
     if (cap >= 25) { outp[23] = h->storage16; outp[24] = h->inited ? h->storage_auto : -1; }
     if (cap >= 26) outp[25] = h->lev16_builds;
+    if (cap >= 28) {            // the dense pass's memoised group sums (option dense_memo): bytes held, full groups of the pass out[8] describes
+        int64_t dm[2] = {0, 0};
+        if (h->inited && be_dense_memo_info) be_dense_memo_info(h->be, h->c, dm);
+        outp[26] = dm[0]; outp[27] = dm[1];
+    }
     return VRG_OK;
 }
 

@@ -153,6 +153,21 @@ __global__ void k_build_lev16(VrgCtx c, uint16_t* dst) {
     VOXEL_LOOP(c) { int x, y, z; uint32_t idx = real_idx(c, t, x, y, z); dst[idx] = (uint16_t)vrg_level_of(c, vrg_voxel_value(c, idx)); }
 }
 
+// 16-bit storage, the dense pass's memo (option dense_memo): gsum[g] = the sum of the values the pass would add for the 256 voxels
+// of group g (unit g >> 2, class byte g & 3: voxels 256 g + 4 lane + 0..3).  One wave per group; the order of the additions
+// is fixed and does not depend on the grid: every lane adds its four values in voxel order, then the butterfly of wave_sum.
+__global__ void __launch_bounds__(TPB) k_build_gsum(const uint16_t* lev16, const double* lev, uint32_t ngroups, double* gsum) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t g = wave; g < ngroups; g += nwaves) {
+        const uint16_t* p = lev16 + ((size_t)g << 8) + (lane << 2);
+        double s = (double)(float)lev[p[0]];
+        s += (double)(float)lev[p[1]]; s += (double)(float)lev[p[2]]; s += (double)(float)lev[p[3]];
+        s = wave_sum(s);
+        if (lane == 0) gsum[g] = s;
+    }
+}
+
 const size_t kElem[7] = {1, 2, 2, 4, 8, 4, 8};
 
 // strides must describe a dense permutation of the three axes (numpy C or F order)
@@ -210,6 +225,7 @@ void be_destroy(VrgBackend* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->rsv) (void)hipFree(b->rsv);
+    if (b->gsum) (void)hipFree(b->gsum);
     if (b->sa) (void)hipStreamSynchronize(b->sa);
     if (b->sb) (void)hipStreamSynchronize(b->sb);
     if (b->comm) { ncclCommDestroy(b->comm); b->comm = nullptr; }
@@ -238,6 +254,7 @@ void be_set_tuning(VrgBackend* b, const char* name, long long v) {
     if (std::strcmp(name, "band_hint") == 0) b->band_hint = (uint32_t)std::min<long long>(std::max<long long>(v, 0), 0x7fffffff);
     if (std::strcmp(name, "direct_hint") == 0) b->direct_hint = v != 0;
     if (std::strcmp(name, "dense_pipe") == 0) b->dense_pipe = (int)v;
+    if (std::strcmp(name, "dense_memo") == 0) b->dense_memo = v < 0 ? -1 : (v != 0);
     if (std::strcmp(name, "memo_above") == 0 && v >= 0) b->memo_above = (uint32_t)std::min<long long>(v, 0x7fffffff);
     if (std::strcmp(name, "verify_every") == 0 && v >= 0) b->verify_every = (int)std::min<long long>(v, 1 << 20);
     if (std::strcmp(name, "small_flips") == 0 && v >= 0) b->small_flips = (uint32_t)std::min<long long>(v, NF_WIDE);
@@ -250,7 +267,12 @@ void be_set_tuning(VrgBackend* b, const char* name, long long v) {
     if (std::strcmp(name, "prio_mode") == 0 && v >= 0 && v <= 2 && v != b->prio_mode) { b->prio_mode = (int)v; make_streams(b); }
 }
 void* be_alloc(VrgBackend* b, size_t bytes) { use_device(b); void* p = nullptr; if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
-void be_free(VrgBackend* b, void* p) { use_device(b); HIP_CHECK(hipFree(p)); }
+static void drop_gsum(VrgBackend* b) { if (b->gsum) HIP_CHECK(hipFree(b->gsum)); b->gsum = nullptr; b->gsum_bytes = 0; b->gsum_for = nullptr; }
+void be_free(VrgBackend* b, void* p) {
+    use_device(b);
+    if (p && p == (const void*)b->gsum_for) drop_gsum(b);        // (the engine drops the 16-bit level indices: their group sums go with them)
+    HIP_CHECK(hipFree(p));
+}
 void be_fill(VrgBackend* b, void* p, int byte, size_t bytes) { use_device(b); HIP_CHECK(hipMemsetAsync(p, byte, bytes, b->sa)); }
 void be_upload(VrgBackend* b, void* dst, const void* src, size_t bytes) { use_device(b); HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, b->sa)); HIP_CHECK(hipStreamSynchronize(b->sa)); }
 void be_download(VrgBackend* b, void* dst, const void* src, size_t bytes) { use_device(b); HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, b->sa)); HIP_CHECK(hipStreamSynchronize(b->sa)); }
@@ -523,6 +545,16 @@ void be_build_lev16(VrgBackend* b, const VrgCtx& c, uint16_t* dst) {
     use_device(b);
     HIP_CHECK(hipMemsetAsync(dst, 0, ((size_t)c.PV + 1023) / 1024 * 1024 * 2, b->sa));
     k_build_lev16<<<voxel_blocks(c), TPB, 0, b->sa>>>(c, dst);
+    // ... and the sums of their 256-voxel groups (the dense pass's memo): rebuilt whenever the indices are.  Without the memory for
+    // them (8 B per 256 voxels) the pass counts every group voxel by voxel.
+    const size_t ngroups = ((size_t)c.PV + 1023) / 1024 * 4;
+    if (b->gsum_bytes != ngroups * sizeof(double)) {
+        drop_gsum(b);
+        if (hipMalloc((void**)&b->gsum, ngroups * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); b->gsum = nullptr; return; }
+        b->gsum_bytes = ngroups * sizeof(double);
+    }
+    b->gsum_for = dst;
+    k_build_gsum<<<4096, TPB, 0, b->sa>>>(dst, c.lev, (uint32_t)ngroups, b->gsum);
 }
 
 void be_init_band(VrgBackend* b, const VrgCtx& c) {

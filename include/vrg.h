@@ -111,6 +111,14 @@ const char* vrg_last_error(const vrg_handle* h);
  *                    the whole slab.  Same sums bit for bit.
  *   "nt_loads"       any time; -1 (default): the dense pass uses non-temporal loads when it fetches more than the
  *                    Infinity Cache can keep (about 300 MB per pass) and ordinary loads below that; 0 / 1 force one
+ *   "dense_memo"     any time; 16-bit storage with skip_excluded: the dense pass takes the intensity sum of every group of 256
+ *                    aligned voxels that are all outer (label 2 or 3) from a table built once per volume with the level
+ *                    indices (8 B per 256 padded voxels: 16 MB at 880x880x640, vrg_get_stats out[26]) instead of fetching the
+ *                    group's indices and looking its values up; every class bit is still read and counted every sweep.
+ *                    -1 (default): volumes of more than 100 000 units of 1024 padded voxels, where it pays; 1: every 16-bit pass;
+ *                    0: none (the kernel of before, bit for bit).  The sums of such groups are added in another order:
+ *                    sum_in / sum_out are bit-identical on data whose partial sums are exact (integers, coarse
+ *                    quantisations) and differ in the last bits otherwise.
  *   "verify_every"   any time; n = 1 (default): the dense pass over every voxel - the reference's recount of innerSize /
  *                    outerSize (:113-116), here a CHECK of the sizes the decisions read (kept by increments) and the source
  *                    of the trace's intensity sums - runs after every sweep; n > 1: after every n-th sweep; 0: never.
@@ -177,7 +185,10 @@ int vrg_get_levels(vrg_handle* h, double* values, int32_t* hist_in, int32_t* his
  * within two voxels of the flip), since the handle was created.
  * With cap >= 25 also who chose the storage of out[10]: out[23] = option storage16 (-1 automatic, 0 never, 1 always), out[24] = what the automatic mode
  * decided at the last vrg_init (1: 16-bit storage, 0: the stored type; -1: the option decided, or not initialised).  With cap >= 26 also out[25] = how
- * often the 16-bit index volume was built since the handle was created (once per volume: a re-init after vrg_set_labels reuses it). */
+ * often the 16-bit index volume was built since the handle was created (once per volume: a re-init after vrg_set_labels reuses it).
+ * With cap >= 28 also the memoised group sums of the 16-bit dense pass (option dense_memo): out[26] = their bytes (0: none built), out[27] = the
+ * all-outer groups of the pass out[8] describes (0 when the pass does not memoise); out[8] then counts no intensity lines for those groups and
+ * 32 B of sums more per listed unit. */
 int vrg_get_stats(vrg_handle* h, int64_t* out, int64_t cap);
 
 /* Diagnostic builds only (compiled with -DVRG_STAMPS, tools/chain_stamps.py): 64 in-kernel time stamps (100-MHz ticks) of
