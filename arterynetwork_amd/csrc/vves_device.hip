@@ -165,21 +165,70 @@ __global__ void __launch_bounds__(COL_T) k_ves_axis1(Ptrs<3> in, double* __restr
     });
 }
 
-// eigenvalues of the symmetric 3x3 matrix, closed form (Smith 1961): e[0] <= e[1] <= e[2]
+// eigenvalues of the symmetric 3x3 matrix: e[0] <= e[1] <= e[2].  Deflation (Eberly, "A robust eigensolver for 3x3 symmetric
+// matrices"; Kopp 2008) on B = (A - q I) / p, whose eigenvalues beta sum to 0, their squares to 6: the roots of
+// beta^3 - 3 beta - 2h, h = det B / 2 in [-1, 1].
+//   The root on the side of h's sign lies in [sqrt 3, 2] in magnitude, at least sqrt 3 from the other two: a simple, well
+//   conditioned root, taken by Newton steps from the chord (which is within 0.014 of it; the fifth step changes nothing).
+//   The other two coincide at h = +-1, where the closed trigonometric form (Smith 1961: acos h, one ulp of h being sqrt(eps)
+//   in the angle) leaves them 1e-8 |A| off.  They come from the 2x2 block of B on the plane orthogonal to the first one's
+//   eigenvector, which is the longest cross product of two rows of B - beta I (their lengths are the two gaps' product times
+//   |v_i|: never all small).
+// -B takes the place of B where h < 0, so that the isolated eigenvalue is always the top one.  Selects only: no branch but
+// the flat case, no indexed array, nothing transcendental.  tests/vesselness_model.py restates it operation by operation
+// (eig3_deflation).
 __device__ __forceinline__ void eig3(double a00, double a11, double a22, double a01, double a02, double a12, double (&e)[3]) {
     const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
     const double q = (a00 + a11 + a22) / 3.0;
     const double d0 = a00 - q, d1 = a11 - q, d2 = a22 - q;
     const double p2 = d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * p1;
-    if (!(p2 > 0.0)) { e[0] = e[1] = e[2] = q; return; }
-    const double p = sqrt(p2 / 6.0), ip = 1.0 / p;
-    const double b00 = d0 * ip, b11 = d1 * ip, b22 = d2 * ip, b01 = a01 * ip, b02 = a02 * ip, b12 = a12 * ip;
+    const double p = sqrt(p2 / 6.0);
+    if (!(p > 0.0)) { e[0] = e[1] = e[2] = q; return; }        // (three equal eigenvalues, or p2 underflows: 1 / p stays finite below)
+    const double ip = 1.0 / p;
+    double b00 = d0 * ip, b11 = d1 * ip, b22 = d2 * ip, b01 = a01 * ip, b02 = a02 * ip, b12 = a12 * ip;
     double h = 0.5 * (b00 * (b11 * b22 - b12 * b12) - b01 * (b01 * b22 - b12 * b02) + b02 * (b01 * b12 - b11 * b02));
     h = fmin(1.0, fmax(-1.0, h));
-    const double phi = acos(h) / 3.0;
-    e[2] = q + 2.0 * p * cos(phi);
-    e[0] = q + 2.0 * p * cos(phi + 2.0943951023931954923);
-    e[1] = 3.0 * q - e[0] - e[2];
+    const double sg = h < 0.0 ? -1.0 : 1.0;
+    b00 *= sg; b11 *= sg; b22 *= sg; b01 *= sg; b02 *= sg; b12 *= sg;
+    const double ah = fabs(h);
+    double beta = 1.7320508075688772 + 0.2679491924311228 * ah;  // sqrt 3 .. 2
+#pragma unroll
+    for (int it = 0; it < 5; it++) beta -= (beta * (beta * beta - 3.0) - 2.0 * ah) / (3.0 * beta * beta - 3.0);
+    // the eigenvector v: rows r0 r1 r2 of B - beta I, the longest of r0 x r1, r0 x r2, r1 x r2
+    const double r00 = b00 - beta, r11 = b11 - beta, r22 = b22 - beta;
+    double c0 = b01 * b12 - b02 * r11, c1 = b02 * b01 - r00 * b12, c2 = r00 * r11 - b01 * b01;       // r0 x r1
+    double n = c0 * c0 + c1 * c1 + c2 * c2;
+    {
+        const double o0 = b01 * r22 - b02 * b12, o1 = b02 * b02 - r00 * r22, o2 = r00 * b12 - b01 * b02;   // r0 x r2
+        const double m = o0 * o0 + o1 * o1 + o2 * o2;
+        const bool take = m > n;
+        c0 = take ? o0 : c0; c1 = take ? o1 : c1; c2 = take ? o2 : c2; n = take ? m : n;
+    }
+    {
+        const double o0 = r11 * r22 - b12 * b12, o1 = b12 * b02 - b01 * r22, o2 = b01 * b12 - r11 * b02;   // r1 x r2
+        const double m = o0 * o0 + o1 * o1 + o2 * o2;
+        const bool take = m > n;
+        c0 = take ? o0 : c0; c1 = take ? o1 : c1; c2 = take ? o2 : c2; n = take ? m : n;
+    }
+    double inv = 1.0 / sqrt(n);
+    const double v0 = c0 * inv, v1 = c1 * inv, v2 = c2 * inv;
+    // u orthogonal to v from v2 and the larger of v0, v1 (their squares sum to 1/2 at least); w = v x u
+    const bool first = fabs(v0) > fabs(v1);
+    const double k = first ? v0 : v1;
+    inv = 1.0 / sqrt(k * k + v2 * v2);
+    const double u0 = first ? -v2 * inv : 0.0, u1 = first ? 0.0 : v2 * inv, u2 = first ? v0 * inv : -v1 * inv;
+    const double w0 = v1 * u2 - v2 * u1, w1 = v2 * u0 - v0 * u2, w2 = v0 * u1 - v1 * u0;
+    // the block [[u.Bu, w.Bu], [w.Bu, w.Bw]]: mean -+ hypot(half the diagonal's difference, off-diagonal)
+    const double x0 = b00 * u0 + b01 * u1 + b02 * u2, x1 = b01 * u0 + b11 * u1 + b12 * u2, x2 = b02 * u0 + b12 * u1 + b22 * u2;
+    const double y0 = b00 * w0 + b01 * w1 + b02 * w2, y1 = b01 * w0 + b11 * w1 + b12 * w2, y2 = b02 * w0 + b12 * w1 + b22 * w2;
+    const double m00 = u0 * x0 + u1 * x1 + u2 * x2, m01 = w0 * x0 + w1 * x1 + w2 * x2, m11 = w0 * y0 + w1 * y1 + w2 * y2;
+    const double mean = 0.5 * (m00 + m11), half = 0.5 * (m00 - m11);
+    const double hyp = sqrt(half * half + m01 * m01);             // (entries of order 1: no overflow to guard against)
+    const double lo = mean - hyp, hi = mean + hyp;
+    const bool pos = sg > 0.0;
+    e[0] = q + p * (pos ? lo : -beta);
+    e[1] = q + p * (pos ? hi : -hi);
+    e[2] = q + p * (pos ? beta : -lo);
 }
 
 struct Measure {
