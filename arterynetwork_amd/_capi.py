@@ -303,8 +303,8 @@ class Session:
 
     def stats(self):
         """Diagnostics: how often a trip was handed back to the host and why, array capacities."""
-        a = (C.c_int64 * 28)()
-        self._check(self.lib.get_stats(self._h, a, 28))
+        a = (C.c_int64 * 30)()
+        self._check(self.lib.get_stats(self._h, a, 30))
         if a[14]:
             dense_kernel = 'k_recount_pipe<3,{}>'.format('true' if a[9] else 'false')
         else:
@@ -319,6 +319,9 @@ class Session:
                 'storage16_option': a[23], 'storage16_auto': None if a[24] < 0 else bool(a[24]), 'level_index_builds': a[25],
                 # option dense_memo (16-bit storage): bytes of the per-group intensity sums, and the all-outer groups of the pass dense_bytes describes
                 'dense_memo_bytes': a[26], 'dense_memo_groups': a[27],
+                # dense_memo = 2: bytes of the tables built at init (per group the sum and the number of its included voxels), and the memoised
+                # groups of fewer than 256 voxels of that pass
+                'dense_rim_bytes': a[28], 'dense_rim_groups': a[29],
                 'dense_nt_loads': bool(a[9]), 'dense_workgroups': a[11], 'dense_listed_units': a[13]}
 
     def nlevels(self):

@@ -81,10 +81,14 @@ struct VrgBackend {
     int nt_loads = -1;                                // option "nt_loads": -1 = by the size of the pass, 0 / 1 = ordinary / non-temporal loads
     int verify_every = 1;                             // option "verify_every": the dense pass on every n-th sweep only (0: never)
     int dense_pipe = 1;                               // option "dense_pipe": fp32 storage + skip_excluded run the two-trips-deep recount (k_recount_pipe)
-    int dense_memo = -1;                              // option "dense_memo": 16-bit storage + skip_excluded take the sums of all-outer 256-voxel groups from gsum (-1: large volumes only, 1: always, 0: never)
+    int dense_memo = -1;                              // option "dense_memo": 16-bit storage + skip_excluded take the sums of all-outer 256-voxel groups from gsum (-1: large volumes only, 1: always, 0: never; 2: the rim groups' sums too, from isum / icnt)
     double* gsum = nullptr; size_t gsum_bytes = 0;    // sum of the values of every 256-voxel group of the padded volume (k_build_gsum), built with the level indices ...
     const uint16_t* gsum_for = nullptr;               // ... at this address (be_build_lev16); freed with them (be_free) or with the backend
     long long memo_groups = 0;                        // full groups be_dense_bytes counted last (stats: dense_memo_groups)
+    double* isum = nullptr; size_t rim_bytes = 0;     // dense_memo = 2: per 256-voxel group the sum of the values of its voxels included at init (f64) and, behind the sums, their
+    const uint16_t* rim_for = nullptr;                // number (u16) - one allocation, built behind the class bits at every init (build_rim) for the level indices at this address; freed with them
+    int rim_auto = 1;                                 // the default (dense_memo = -1) takes the rim groups' memo: decided by what init finds (be_init_finish)
+    long long rim_groups = 0;                         // memoised groups of fewer than 256 voxels be_dense_bytes counted last (stats: dense_rim_groups)
     uint64_t pass_bytes = 0;                          // bytes a dense pass fetches, counted at the end of init (0: not known yet)
     uint32_t memo_above = 32768;                      // option "memo_above": band entries above which a fused trip keeps the per-level memo (k_memo)
     long long memo_trips = 0;                         // fused trips that did
@@ -245,5 +249,6 @@ __device__ void ulist_refresh(const VrgCtx& c, bool force, int p) {
 void use_device(VrgBackend* b);                                                                          // vrg_init.hip
 void init_exact(VrgBackend* b, const VrgCtx& c);                                                         // vrg_chain.hip
 void init_dense(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user);                            // vrg_device.hip
+void build_rim(VrgBackend* b, const VrgCtx& c);                                                          // vrg_init.hip
 void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_t e_stop, be_reduce_fn cb, void* user);   // vrg_device.hip
 #pragma GCC visibility pop

@@ -1,6 +1,7 @@
 // vrg_device.hip - the dense pass of the product backend (vrg_device.h: the overview): k_gate, the recount (k_recount_pipe /
 // k_recount_bits), the class bits and the unit list, the slab close and all-reduce, and their host side - launch sizing included.
 #include "vrg_device.h"
+#include "vrg_rim.h"
 
 namespace {
 
@@ -216,6 +217,36 @@ __device__ __forceinline__ uint32_t full_groups(uint32_t w) {
     for (int j = 0; j < 4; j++) if (__builtin_amdgcn_ballot_w64((x & (0xffu << (8 * j))) != 0u) == 0ull) m |= 1u << j;
     return m;
 }
+// RIM (dense_memo = 2): the groups of a unit's class word whose outer voxels are exactly the voxels that were included at init - no
+// lane holds an inner voxel, and the wave counts as many outer voxels as init counted included ones (ic01, ic23: the unit's four
+// counts, 16 bits each; not 0).  Inclusion is monotone - a voxel never becomes excluded and an excluded one is never included
+// (VB_X is set by init alone) - so the sets are then equal, and the group's outer sum is the sum init formed (k_build_rim).  A full
+// group is the case of 256.  The count is exact: every lane packs its four counts (0..4) into the bytes of one word; five DPP steps
+// add them over each half of the wave (at most 128 per byte), and the two halves meet in scalar registers, where 256 fits.
+// (All 64 lanes take part: the walk's loop is wave-uniform.)
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t x) {
+    return x + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xf, false);      // (a lane without a source adds 0)
+}
+// ne: the groups that hold an included voxel; nouter: the unit's outer voxels.
+__device__ __forceinline__ uint32_t rim_groups(uint32_t w, uint32_t ic01, uint32_t ic23, uint32_t& ne, uint32_t& nouter) {
+    uint32_t x = vrg_rim_pack(w);                                // byte j: this lane's outer voxels of group j (vrg_rim.h)
+    x = dpp_add<0x111, 0xf>(x); x = dpp_add<0x112, 0xf>(x); x = dpp_add<0x114, 0xf>(x); x = dpp_add<0x118, 0xf>(x);    // row_shr 1, 2, 4, 8: lane 15 of a row holds the row's counts
+    x = dpp_add<0x142, 0xa>(x);                                  // row_bcast 15 into rows 1 and 3: lanes 31 and 63 hold a half-wave's
+    const uint32_t a = __builtin_amdgcn_readlane(x, 31), b = __builtin_amdgcn_readlane(x, 63);
+    uint32_t inner = 0u;
+    if (__builtin_amdgcn_ballot_w64((w & 0x55555555u) != 0u) != 0ull) {         // (rare: the region's voxels are few)
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (__builtin_amdgcn_ballot_w64((w & (0x55u << (8 * j))) != 0u) != 0ull) inner |= 1u << j;
+    }
+    return vrg_rim_decide(a, b, inner, ic01, ic23, ne, nouter);
+}
+// the four counts of unit u behind the ngroups sums of the table, as scalar loads
+__device__ __forceinline__ void load_icnt(const double* isum, uint32_t ngroups, uint32_t u, uint32_t& ic01, uint32_t& ic23) {
+    typedef const uint32_t __attribute__((address_space(4))) cu32;
+    const cu32* p = (cu32*)(isum + ngroups) + ((size_t)u << 1);
+    ic01 = p[0]; ic23 = p[1];
+}
 // the four group sums of unit u, as scalar loads like the list entries (written by an earlier kernel only: constant address space)
 __device__ __forceinline__ void load_gsum(const double* gsum, uint32_t u, UnitSums& o) {
     typedef const double __attribute__((address_space(4))) cf64;
@@ -277,7 +308,9 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // sweep take theirs (stats_bits).  The wave adds them in the order it meets them, into an accumulator of their own that
 // joins lane 0's outer sum behind the walk: a fixed order for a given grid, like every other sum of the pass.  The units
 // the slab's faces cut are counted voxel by voxel as ever.
-template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false>
+// RIM (with MEMO; dense_memo = 2): gsum is the table of the sums and counts of the voxels included at init (k_build_rim), and the
+// groups that take their sum from it are those of rim_groups - the full ones among them.  The unit's counts travel with its sums.
+template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false, bool RIM = false>
 __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum) {
     VRG_CHAOS_POINT(7);
     if (check_done && check_done < 3 && !c.dctl[VD_GO]) return;     // the gate says: no sweep to count (the run has stopped) or this sweep's pass is left out
@@ -311,9 +344,11 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     SweepAcc acc = {0, 0, 0.0, 0.0};
     double gacc = 0.0;
     UnitSums gs[UNITS];
+    uint32_t ic[UNITS][2];
+    const uint32_t ngroups = (uint32_t)((((uint64_t)c.PV + 1023u) >> 10) << 2);
     if constexpr (MEMO) {
 #pragma unroll
-        for (int q = 0; q < UNITS; q++) load_gsum(gsum, uu[q], gs[q]);
+        for (int q = 0; q < UNITS; q++) { load_gsum(gsum, uu[q], gs[q]); if constexpr (RIM) load_icnt(gsum, ngroups, uu[q], ic[q][0], ic[q][1]); }
     }
     // the class words of a trip are fetched one trip ahead (the intensity loads depend on them), before this trip's
     // intensities: loads return in order, so they cost no wait of their own
@@ -322,7 +357,66 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     for (int q = 0; q < UNITS; q++) { uu[q] = __builtin_amdgcn_readfirstlane(uu[q]); w[q] = i < n ? load_cls<NT>(cls, uu[q], lane) : 0u; }
 #pragma unroll
     for (int q = 0; q < UNITS; q++) { asm volatile("" : "+v"(w[q])); if (i + q >= n) w[q] = 0u; }   // settle the first trip's class words here: no waits in mid-loop
-    while (i < n) {
+    if constexpr (RIM) {
+        // RIM: the walk of below, everything a trip ahead of where the loop below has it.  A memoising trip issues hardly an intensity load and
+        // forms hardly a sum, so what it would wait for is what it asks for itself: the list entries (a scalar load that misses: the
+        // list is streamed) and then the class words that depend on them.  Here the entries are requested three trips ahead and the class
+        // words two, a unit's sums and counts one - and a trip waits for nothing that was requested less than a trip ago, its own few
+        // intensities excepted.
+        const uint32_t step = nwaves * UNITS;
+        uint32_t un[UNITS], wn[UNITS], u2[UNITS];
+        UnitSums gn[UNITS];
+        uint32_t icn[UNITS][2];
+#pragma unroll
+        for (int q = 0; q < UNITS; q++) { un[q] = 0u; u2[q] = 0u; wn[q] = 0u; }
+        if (i < n) {                                   // (a wave with nothing to walk reads nothing: an empty list has no readable entry)
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) { un[q] = ulist_entry(ulist, min(i + step + q, last)); u2[q] = ulist_entry(ulist, min(i + 2u * step + q, last)); }
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) wn[q] = load_cls<NT>(cls, un[q], lane);    // (unconditionally - a slot past the list's end reads the last unit's and is zeroed where it is used -: the number of loads in flight is static)
+        }
+        uint32_t nmemo = 0u;                       // outer voxels of the trips that went the short way (they join lane 0's count behind the walk)
+        while (i < n) {
+            uint32_t u3[UNITS], w2[UNITS], fm[UNITS], ne[UNITS], no[UNITS];
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) {          // (scalar loads return in any order, so a wait for one is a wait for all: all of a trip's are issued here, and used a trip later)
+                u3[q] = ulist_entry(ulist, min(i + 3u * step + q, last));
+                load_gsum(gsum, un[q], gn[q]); load_icnt(gsum, ngroups, un[q], icn[q][0], icn[q][1]);
+            }
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) w2[q] = load_cls<NT>(cls, u2[q], lane);
+            bool all = true;
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) {
+                if (i + q >= n) w[q] = 0u;                                         // (uniform: slots past the list's end hold nothing)
+                fm[q] = rim_groups(w[q], ic[q][0], ic[q][1], ne[q], no[q]); all = all && fm[q] == ne[q];
+            }
+            if (all) {
+                // every group of the trip that holds an included voxel takes its sum from the table (nearly every trip does): no
+                // intensity load, no per-lane count - the outer voxels are the wave's count - and nothing to wait for
+#pragma unroll
+                for (int q = 0; q < UNITS; q++) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) gacc += ((fm[q] >> j) & 1u) ? gs[q].g[j] : 0.0;      // (+0.0 changes nothing: gacc is never -0.0)
+                    nmemo += no[q];
+                }
+            } else {
+                UnitVals<MODE> f[UNITS];
+#pragma unroll
+                for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, w[q], f[q], fm[q]);
+#pragma unroll
+                for (int q = 0; q < UNITS; q++) stats_bits<MODE, SKIP, true>(acc, w[q], f[q], s_val, fm[q], &gs[q], &gacc, c.L);
+            }
+#pragma unroll
+            for (int q = 0; q < UNITS; q++) {
+                gs[q] = gn[q]; ic[q][0] = icn[q][0]; ic[q][1] = icn[q][1];
+                uu[q] = un[q]; w[q] = wn[q]; un[q] = u2[q]; wn[q] = w2[q]; u2[q] = u3[q];
+            }
+            i += step;
+        }
+        if (lane == 0u) acc.nout += nmemo;
+    }
+    if constexpr (!RIM) while (i < n) {              // (a RIM instantiation has walked its list above: it holds no second walk)
         const uint32_t in = i + nwaves * UNITS;
         uint32_t un[UNITS], wn[UNITS];
 #pragma unroll
@@ -492,7 +586,11 @@ __global__ void k_cls_build(VrgCtx c) {
 // and its class words (256 B; the units the slab's faces cut: always) + every 128-byte intensity line that holds an
 // included voxel (what k_recount_bits<.., SKIP> fetches).  memo (a memoising pass, option dense_memo): a whole unit costs the 32 B
 // of its four group sums more, and a full group of a whole unit - 256 outer voxels - no intensity lines; out[1] counts those groups.
-__global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long long* out, int memo) {
+// memo = 2 (dense_memo = 2, the tables of k_build_rim at isum): a whole unit costs 8 B of counts more still, and a group of a whole unit
+// without an inner voxel whose outer voxels number what init counted (not 0) no intensity lines; out[1] counts those of 256 voxels,
+// out[2] the others.
+__global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long long* out, int memo, const double* isum = nullptr) {
+    const uint16_t* icnt = memo == 2 ? reinterpret_cast<const uint16_t*>(isum + ((((uint64_t)c.PV + 1023u) >> 10) << 2)) : nullptr;
     const uint32_t* __restrict__ cls = c.clsb[vrg_load_i64(&c.dctl[VD_RSEQ]) & 1];
     const uint32_t plane = (uint32_t)c.PY * (uint32_t)c.PX;
     const uint32_t lo = (2u + (uint32_t)c.z0) * plane, hi = (2u + (uint32_t)c.z1) * plane;
@@ -502,16 +600,19 @@ __global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long lon
     const uint32_t lpl = c.lev16 ? 16u : (c.I ? 8u : 4u);          // lanes (of 4 voxels each) per 128-byte line
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-    unsigned long long bytes = 0, full = 0;
+    unsigned long long bytes = 0, full = 0, rim = 0;
     for (uint32_t u = e0 + wave; u <= e1; u += nwaves) {
         const bool whole = u >= f_lo && u < f_hi;
         if (whole && !((c.ubits[u >> 5] >> (u & 31u)) & 1u)) continue;
         uint32_t w = cls[((size_t)u << 6) + lane];
-        bytes += whole ? (memo ? 292u : 260u) : 256u;               // class words (+ the unit's list entry, + its group sums)
+        bytes += whole ? (memo == 2 ? 300u : (memo ? 292u : 260u)) : 256u;      // class words (+ the unit's list entry, + its group sums, + its counts)
         for (int j = 0; j < 4; j++) {
             const uint32_t v = (u << 10) + (j << 8) + (lane << 2);
             const uint32_t wj = (w >> (8 * j)) & 0xffu;
-            if (memo && whole && __ballot(wj != 0xAAu) == 0ull) { full++; continue; }    // (wave-uniform)
+            if (memo == 2 && whole) {                                // (wave-uniform)
+                const uint32_t nout = (uint32_t)wave_sum((long long)__popc(wj & 0xAAu));
+                if (__ballot((wj & 0x55u) != 0u) == 0ull && nout != 0u && nout == icnt[4u * u + j]) { if (nout == 256u) full++; else rim++; continue; }
+            } else if (memo && whole && __ballot(wj != 0xAAu) == 0ull) { full++; continue; }    // (wave-uniform)
             const bool need = v >= lo && v < hi && wj != 0u;
             const uint64_t m = __ballot(need);
             for (uint32_t g = 0; g < 64u; g += lpl) bytes += ((m >> g) & ((1ull << lpl) - 1ull)) ? 128u : 0u;
@@ -519,6 +620,7 @@ __global__ void __launch_bounds__(TPB) k_dense_bytes(VrgCtx c, unsigned long lon
     }
     if (lane == 0 && bytes) atomicAdd(out, bytes);
     if (lane == 0 && full) atomicAdd(out + 1, full);
+    if (lane == 0 && rim) atomicAdd(out + 2, rim);
 }
 
 __global__ void k_dense_pack(VrgCtx c) { vrg_dense_pack(c); }
@@ -543,9 +645,19 @@ bool dense_nt(const VrgBackend* b, const VrgCtx&) {
 // 880x880x640: 0.117 -> 0.095, 1024^3: 0.224 -> 0.170).  The whole volume decides, not the slab, so that the ranks of a group
 // decide alike (as for the automatic 16-bit storage itself); the slab passes of a large volume have not been timed with it.
 // 1: every 16-bit pass; 0: none.
-bool dense_memo(const VrgBackend* b, const VrgCtx& c) {
-    if (!b->dense_memo || !b->skip || !c.lev16 || !b->gsum || b->gsum_for != c.lev16) return false;
-    return b->dense_memo > 0 || ((uint64_t)c.PV >> 10) > 100000;
+// 2: every 16-bit pass, and the rim groups take their sums from a table as well (rim_groups; the tables of this init's labels, build_rim,
+// have to be on hand - the full groups' memo serves otherwise); the default picks 2 wherever it picked 1.  Returns 0, 1 or 2.
+int dense_memo(const VrgBackend* b, const VrgCtx& c) {
+    if (!b->dense_memo || !b->skip || !c.lev16) return 0;
+    const bool large = ((uint64_t)c.PV >> 10) > 100000;
+    if (b->dense_memo < 0 && !large) return 0;
+    // By default only where init found the rim groups to be a fair share of what is memoised (be_init_finish: at least half as many as full
+    // groups - the bench volume has 723 000 against 498 000): without a brain mask a row's end is the only rim group beside three full ones,
+    // (Unlike the size rule above, this one looks at the SLAB: be_init_finish counts the groups of this rank's slab, so the ranks of a Z-slab group
+    // may choose differently between 2 and 1 - and with that between grids.  Every choice counts the same voxels; only the order of the sums differs.)
+    // and the pass measured slower with the tables than without (880x880x640 --no-brain-mask, one run each: 0.0959 -> 0.1115 ms, step 0.0995 -> 0.1175).
+    if (b->dense_memo != 1 && (b->dense_memo == 2 || b->rim_auto) && b->isum && b->rim_for == c.lev16) return 2;
+    return b->gsum && b->gsum_for == c.lev16 ? 1 : 0;
 }
 
 // workgroups of the dense recount: >= 32 one-KiB units per wave, at most 1 workgroup per CU
@@ -568,7 +680,10 @@ int dense_blocks(const VrgBackend* b, const VrgCtx& c) {
     // to cover what a trip still waits for: six workgroups per CU (tools/sweep_recount.py --storage16, 60 sweeps per point, one process per shape,
     // 880x880x640 / 1024^3: 768 -> 0.120 / 0.237, 1024 -> 0.107, 0.107 / 0.204, 0.204, 1280 -> 0.098, 0.099 / 0.188, 1536 -> 0.097, 0.100 / 0.180, 0.181,
     // 1792 -> 0.107, 0.108 / 0.199, 0.206, 2048 -> 0.104 / - ms; before the rim path of stats_group_outer_idx).  Small passes keep their grid.
-    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (dense_memo(b, c) ? 6 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
+    // With the rim groups' memo (dense_memo = 2) a trip is short and waits for nothing it asked for itself, and the pass is flat from 1024 to
+    // 2048 workgroups (tools/sweep_recount.py 880x880x640 --storage16, 60 sweeps per point, one process: 256 -> 0.166, 512 -> 0.105, 0.106,
+    // 768 -> 0.090, 1024 -> 0.085, 0.085, 1280 -> 0.090, 1536 -> 0.089, 2048 -> 0.084 ms; profiles/dense_rim_ab_880.json): four per CU again.
+    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (dense_memo(b, c) == 1 ? 6 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
     // fp32: whole or half multiples of the CU count only - 552 or 640 workgroups leave some CUs with a wave more than others for
     // the whole pass (880x880x160: 552 -> 0.058 ms, 384 -> 0.050; 880x880x320: 640 -> 0.103, 512 -> 0.094, 768 -> 0.091 but a
     // slower step, 0.1035 vs 0.1003, the band chain queueing behind three waves per SIMD); one session, tools/gpu_slabsweep.sh
@@ -635,10 +750,15 @@ static bool dense_deep(const VrgBackend* b, const VrgCtx& c) { return b->dense_p
 // The start / stop events ride on the dispatch itself (hipExtLaunchKernel): no separate event packets in the stream,
 // which cost ~4 us each between two back-to-back recounts.
 template <bool NT, bool SKIP>
-static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, const double* gsum, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, const double* gsum, bool rim, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
     const double* const none = nullptr;
     if constexpr (SKIP) {
         if (deep) { hipExtLaunchKernelGGL((k_recount_pipe<3, NT>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check); return; }
+        if (gsum && rim) {     // (dense_memo = 2: gsum is the table of build_rim)
+            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum);
+            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum);
+            return;
+        }
         if (gsum) {            // (dense_memo: 16-bit storage)
             if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum);
             else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum);
@@ -660,14 +780,16 @@ static void launch_recount(VrgBackend* b, const VrgCtx& c, int check, hipStream_
     const int blocks = dense_blocks(b, c);
     const bool nt = dense_nt(b, c), deep = dense_deep(b, c) && check != 0 && check != 3;
     if (check == 1 || check == 2) k_gate<<<1, GATE_THREADS, 0, st>>>(c, b->verify_every, check);
-    const double* const gsum = dense_memo(b, c) ? b->gsum : nullptr;
-    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, gsum, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, gsum, st, e_start, e_stop); }
-    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, nullptr, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, nullptr, st, e_start, e_stop); }
+    const int memo = dense_memo(b, c);
+    const double* const gsum = memo == 2 ? b->isum : (memo ? b->gsum : nullptr);
+    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, gsum, memo == 2, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, gsum, memo == 2, st, e_start, e_stop); }
+    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, nullptr, false, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, nullptr, false, st, e_start, e_stop); }
 }
 
 // init: the class bits and the unit list from the labels, then the first count (the sizes the sweeps keep by increments start from it)
 void init_dense(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     k_cls_build<<<2048, TPB, 0, b->sa>>>(c);
+    build_rim(b, c);                     // (dense_memo = 2: what each 256-voxel group includes at init, behind the class bits; the first count may use it)
     k_ulist_init<<<1, GATE_THREADS, 0, b->sa>>>(c);
     launch_recount(b, c, 0, b->sa);
     reduce_dense(b, c, cb, user, b->sa);
@@ -725,23 +847,26 @@ void be_dense_info(VrgBackend* b, const VrgCtx& c, int64_t out[5]) {
 }
 uint64_t be_dense_bytes(VrgBackend* b, const VrgCtx& c) {
     use_device(b);
-    b->memo_groups = 0;
-    if (!b->skip) {            // every voxel of the slab's units is streamed
+    b->memo_groups = 0; b->rim_groups = 0;
+    if (!b->skip) {           // every voxel of the slab's units is streamed
         const uint64_t plane = (uint64_t)c.PY * c.PX, lo = (2u + (uint64_t)c.z0) * plane, hi = (2u + (uint64_t)c.z1) * plane;
         const uint64_t bpv4 = c.lev16 ? 9 : (c.I ? 17 : 33);      // 4 x (intensity bytes + 0.25)
         return (hi - lo) * bpv4 / 4;
     }
     HIP_CHECK(hipStreamSynchronize(b->sb));
-    unsigned long long* d = nullptr; unsigned long long v[2] = {0, 0};
-    HIP_CHECK(hipMalloc(&d, 16));
+    unsigned long long* d = nullptr; unsigned long long v[3] = {0, 0, 0};
+    HIP_CHECK(hipMalloc(&d, 24));
     if (!d) return 0;
-    HIP_CHECK(hipMemsetAsync(d, 0, 16, b->sa));
-    k_dense_bytes<<<ITEM_BLOCKS, TPB, 0, b->sa>>>(c, d, dense_memo(b, c) ? 1 : 0);
-    HIP_CHECK(hipMemcpyAsync(v, d, 16, hipMemcpyDeviceToHost, b->sa));
+    HIP_CHECK(hipMemsetAsync(d, 0, 24, b->sa));
+    const int memo = dense_memo(b, c);
+    k_dense_bytes<<<ITEM_BLOCKS, TPB, 0, b->sa>>>(c, d, memo, memo == 2 ? b->isum : nullptr);
+    HIP_CHECK(hipMemcpyAsync(v, d, 24, hipMemcpyDeviceToHost, b->sa));
     HIP_CHECK(hipStreamSynchronize(b->sa));
     HIP_CHECK(hipFree(d));
-    b->memo_groups = (long long)v[1];
+    b->memo_groups = (long long)v[1]; b->rim_groups = (long long)v[2];
     return v[0];
 }
+// the rim groups' tables of this handle (dense_memo = 2): {bytes held, memoised groups of fewer than 256 voxels be_dense_bytes last counted}
+void be_dense_rim_info(VrgBackend* b, const VrgCtx&, int64_t out[2]) { out[0] = b->isum ? (int64_t)b->rim_bytes : 0; out[1] = b->rim_groups; }
 // the memoised group sums of this handle: {bytes held, full groups be_dense_bytes last counted}
 void be_dense_memo_info(VrgBackend* b, const VrgCtx&, int64_t out[2]) { out[0] = b->gsum ? (int64_t)b->gsum_bytes : 0; out[1] = b->memo_groups; }

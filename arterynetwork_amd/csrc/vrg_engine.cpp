@@ -17,6 +17,9 @@
 // An extension only the device backend has (vrg_device.hip; null where the engine is linked with a backend that lacks it): its memoised
 // group sums of the 16-bit dense pass - out[0] = bytes held, out[1] = all-outer groups counted by the last be_dense_bytes.
 __attribute__((weak)) void be_dense_memo_info(VrgBackend* b, const VrgCtx& c, int64_t out[2]);
+// ... and the tables of its rim groups (dense_memo = 2) - out[0] = bytes held, out[1] = memoised groups of fewer than 256 voxels counted
+// by the last be_dense_bytes.
+__attribute__((weak)) void be_dense_rim_info(VrgBackend* b, const VrgCtx& c, int64_t out[2]);
 
 #ifndef VRG_API_PREFIX
 #define VRG_API_PREFIX vrg_
@@ -838,7 +841,8 @@ int API(get_levels)(vrg_handle* h, double* values, int32_t* hin, int32_t* hout, 
 // out[8] = bytes one dense pass requests from memory with the current labels (0 before init); with cap >= 14 also how the
 // dense pass is launched: out[9] = non-temporal loads, out[10] = storage (0 fp32, 1 u16 level index, 2 f64), out[11] =
 // workgroups, out[12] = skip_excluded, out[13] = listed units; with cap >= 28 out[26] = bytes of the dense pass's memoised group sums,
-// out[27] = all-outer groups of the pass out[8] describes
+// out[27] = all-outer groups of the pass out[8] describes; with cap >= 30 out[28] = bytes of the rim groups' tables (dense_memo = 2),
+// out[29] = memoised groups of fewer than 256 voxels of that pass
 int API(get_stats)(vrg_handle* h, int64_t* outp, int64_t cap) {
     if (!h || !outp || cap < 8) return VRG_E_ARG;
     for (int i = 0; i < 4; i++) outp[i] = h->bails[i];
@@ -871,6 +875,11 @@ int API(get_stats)(vrg_handle* h, int64_t* outp, int64_t cap) {
         int64_t dm[2] = {0, 0};
         if (h->inited && be_dense_memo_info) be_dense_memo_info(h->be, h->c, dm);
         outp[26] = dm[0]; outp[27] = dm[1];
+    }
+    if (cap >= 30) {            // ... and of its rim groups (dense_memo = 2): bytes of the two tables, memoised groups of fewer than 256 voxels of that pass
+        int64_t dr[2] = {0, 0};
+        if (h->inited && be_dense_rim_info) be_dense_rim_info(h->be, h->c, dr);
+        outp[28] = dr[0]; outp[29] = dr[1];
     }
     return VRG_OK;
 }

@@ -168,6 +168,23 @@ __global__ void __launch_bounds__(TPB) k_build_gsum(const uint16_t* lev16, const
     }
 }
 
+// ... and the memo of the rim groups (dense_memo = 2): isum[g] = the same sum over the voxels of group g that are included (class
+// not 0) in the class bits as init has just built them, an excluded voxel adding +0.0 - the same additions in the same order, so a
+// group without excluded voxels gets gsum[g] bit for bit -, and icnt[g] = how many they are (0..256).
+__global__ void __launch_bounds__(TPB) k_build_rim(const uint32_t* cls, const uint16_t* lev16, const double* lev, uint32_t ngroups, double* isum, uint16_t* icnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t g = wave; g < ngroups; g += nwaves) {
+        const uint32_t wj = (cls[((size_t)(g >> 2) << 6) + lane] >> (8u * (g & 3u))) & 0xffu;
+        const uint16_t* p = lev16 + ((size_t)g << 8) + (lane << 2);
+        double s = (wj & 0x03u) ? (double)(float)lev[p[0]] : 0.0;
+        s += (wj & 0x0cu) ? (double)(float)lev[p[1]] : 0.0; s += (wj & 0x30u) ? (double)(float)lev[p[2]] : 0.0; s += (wj & 0xc0u) ? (double)(float)lev[p[3]] : 0.0;
+        s = wave_sum(s);
+        const long long n = wave_sum((long long)__popc((wj | (wj >> 1)) & 0x55u));
+        if (lane == 0) { isum[g] = s; icnt[g] = (uint16_t)n; }
+    }
+}
+
 const size_t kElem[7] = {1, 2, 2, 4, 8, 4, 8};
 
 // strides must describe a dense permutation of the three axes (numpy C or F order)
@@ -226,6 +243,7 @@ void be_destroy(VrgBackend* b) {
     (void)hipSetDevice(b->device);
     if (b->rsv) (void)hipFree(b->rsv);
     if (b->gsum) (void)hipFree(b->gsum);
+    if (b->isum) (void)hipFree(b->isum);
     if (b->sa) (void)hipStreamSynchronize(b->sa);
     if (b->sb) (void)hipStreamSynchronize(b->sb);
     if (b->comm) { ncclCommDestroy(b->comm); b->comm = nullptr; }
@@ -254,7 +272,7 @@ void be_set_tuning(VrgBackend* b, const char* name, long long v) {
     if (std::strcmp(name, "band_hint") == 0) b->band_hint = (uint32_t)std::min<long long>(std::max<long long>(v, 0), 0x7fffffff);
     if (std::strcmp(name, "direct_hint") == 0) b->direct_hint = v != 0;
     if (std::strcmp(name, "dense_pipe") == 0) b->dense_pipe = (int)v;
-    if (std::strcmp(name, "dense_memo") == 0) b->dense_memo = v < 0 ? -1 : (v != 0);
+    if (std::strcmp(name, "dense_memo") == 0) b->dense_memo = v < 0 ? -1 : (v == 2 ? 2 : (v != 0));
     if (std::strcmp(name, "memo_above") == 0 && v >= 0) b->memo_above = (uint32_t)std::min<long long>(v, 0x7fffffff);
     if (std::strcmp(name, "verify_every") == 0 && v >= 0) b->verify_every = (int)std::min<long long>(v, 1 << 20);
     if (std::strcmp(name, "small_flips") == 0 && v >= 0) b->small_flips = (uint32_t)std::min<long long>(v, NF_WIDE);
@@ -268,9 +286,11 @@ void be_set_tuning(VrgBackend* b, const char* name, long long v) {
 }
 void* be_alloc(VrgBackend* b, size_t bytes) { use_device(b); void* p = nullptr; if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
 static void drop_gsum(VrgBackend* b) { if (b->gsum) HIP_CHECK(hipFree(b->gsum)); b->gsum = nullptr; b->gsum_bytes = 0; b->gsum_for = nullptr; }
+static void drop_rim(VrgBackend* b) { if (b->isum) HIP_CHECK(hipFree(b->isum)); b->isum = nullptr; b->rim_bytes = 0; b->rim_for = nullptr; }
 void be_free(VrgBackend* b, void* p) {
     use_device(b);
     if (p && p == (const void*)b->gsum_for) drop_gsum(b);        // (the engine drops the 16-bit level indices: their group sums go with them)
+    if (p && p == (const void*)b->rim_for) drop_rim(b);
     HIP_CHECK(hipFree(p));
 }
 void be_fill(VrgBackend* b, void* p, int byte, size_t bytes) { use_device(b); HIP_CHECK(hipMemsetAsync(p, byte, bytes, b->sa)); }
@@ -547,6 +567,7 @@ void be_build_lev16(VrgBackend* b, const VrgCtx& c, uint16_t* dst) {
     k_build_lev16<<<voxel_blocks(c), TPB, 0, b->sa>>>(c, dst);
     // ... and the sums of their 256-voxel groups (the dense pass's memo): rebuilt whenever the indices are.  Without the memory for
     // them (8 B per 256 voxels) the pass counts every group voxel by voxel.
+    drop_rim(b);                               // (the rim groups' tables belong to the old indices: the next init builds them anew, build_rim)
     const size_t ngroups = ((size_t)c.PV + 1023) / 1024 * 4;
     if (b->gsum_bytes != ngroups * sizeof(double)) {
         drop_gsum(b);
@@ -555,6 +576,22 @@ void be_build_lev16(VrgBackend* b, const VrgCtx& c, uint16_t* dst) {
     }
     b->gsum_for = dst;
     k_build_gsum<<<4096, TPB, 0, b->sa>>>(dst, c.lev, (uint32_t)ngroups, b->gsum);
+}
+
+// The rim groups' tables (dense_memo = 2; k_build_rim), from the class bits init_dense has just built: at EVERY init - the labels may
+// be new - and only with 16-bit storage.  One allocation of 10 B per group, the sums in front.  Without the memory for it the pass
+// runs without them (dense_memo in vrg_device.hip).
+void build_rim(VrgBackend* b, const VrgCtx& c) {
+    // ... and only where the option can select them: not with dense_memo = 0 or 1, nor by default on a volume of up to 100 000 units
+    if (!c.lev16 || !b->skip || b->dense_memo == 0 || b->dense_memo == 1 || (b->dense_memo < 0 && ((uint64_t)c.PV >> 10) <= 100000)) { drop_rim(b); return; }
+    const size_t ngroups = ((size_t)c.PV + 1023) / 1024 * 4;
+    if (b->rim_bytes != ngroups * 10) {
+        drop_rim(b);
+        if (hipMalloc((void**)&b->isum, ngroups * 10) != hipSuccess) { (void)hipGetLastError(); b->isum = nullptr; return; }
+        b->rim_bytes = ngroups * 10;
+    }
+    b->rim_for = c.lev16;
+    k_build_rim<<<4096, TPB, 0, b->sa>>>(c.clsb[0], c.lev16, c.lev, (uint32_t)ngroups, b->isum, reinterpret_cast<uint16_t*>(b->isum + ngroups));
 }
 
 void be_init_band(VrgBackend* b, const VrgCtx& c) {
@@ -586,9 +623,12 @@ void be_init_finish(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user)
     else k_hist_voxel<<<voxel_blocks(c), TPB, 0, b->sa>>>(c);
     if (c.nb) be_build_bins(b, c);              // (large level table: the histograms also as bin moments, before the first exact densities)
     init_exact(b, c);
+    b->rim_auto = 1;                            // (the first count may use the rim groups' tables: its sums are the same either way)
     init_dense(b, c, cb, user);
     k_fin_init<<<1, 1, 0, b->sa>>>(c);
     b->pass_bytes = be_dense_bytes(b, c);       // (decides between ordinary and non-temporal loads for the sweeps' passes)
+    // the default keeps the rim groups' memo only where there are rim groups to speak of (dense_memo in vrg_device.hip): counted just now
+    if (b->dense_memo < 0 && b->rim_groups * 2 < b->memo_groups) { b->rim_auto = 0; b->pass_bytes = be_dense_bytes(b, c); }
 }
 
 void be_events_collect(VrgBackend* b, VrgEvents* ev, long long n_valid) {

@@ -115,8 +115,15 @@ const char* vrg_last_error(const vrg_handle* h);
  *                    aligned voxels that are all outer (label 2 or 3) from a table built once per volume with the level
  *                    indices (8 B per 256 padded voxels: 16 MB at 880x880x640, vrg_get_stats out[26]) instead of fetching the
  *                    group's indices and looking its values up; every class bit is still read and counted every sweep.
- *                    -1 (default): volumes of more than 100 000 units of 1024 padded voxels, where it pays; 1: every 16-bit pass;
- *                    0: none (the kernel of before, bit for bit).  The sums of such groups are added in another order:
+ *                    2: every 16-bit pass, and a group that mixes outer and excluded voxels (the rim of the brain mask) takes its
+ *                    outer sum from a table as well: per group the sum and the number of the voxels included at vrg_init (10 B per
+ *                    256 padded voxels, rebuilt at every vrg_init; out[28]), used whenever the group holds no inner voxel and
+ *                    exactly that many outer voxels - inclusion is monotone (a voxel only ever goes 4 -> 3), so its outer set
+ *                    is then the included set of vrg_init.  Without the memory for the tables the pass runs as with 1; the tables
+ *                    are built by vrg_init only where the option then selects them, so a change to 2 takes effect at the next vrg_init.
+ *                    -1 (default): volumes of more than 100 000 units of 1024 padded voxels, where it pays - as with 2 where
+ *                    vrg_init finds at least half as many such mixed groups as all-outer ones, as with 1 otherwise; 1: every
+ *                    16-bit pass, all-outer groups only; 0: none (the kernel of before, bit for bit).  The sums of such groups are added in another order:
  *                    sum_in / sum_out are bit-identical on data whose partial sums are exact (integers, coarse
  *                    quantisations) and differ in the last bits otherwise.
  *   "verify_every"   any time; n = 1 (default): the dense pass over every voxel - the reference's recount of innerSize /
@@ -188,7 +195,8 @@ int vrg_get_levels(vrg_handle* h, double* values, int32_t* hist_in, int32_t* his
  * often the 16-bit index volume was built since the handle was created (once per volume: a re-init after vrg_set_labels reuses it).
  * With cap >= 28 also the memoised group sums of the 16-bit dense pass (option dense_memo): out[26] = their bytes (0: none built), out[27] = the
  * all-outer groups of the pass out[8] describes (0 when the pass does not memoise); out[8] then counts no intensity lines for those groups and
- * 32 B of sums more per listed unit. */
+ * 32 B of sums more per listed unit.  With cap >= 30 also the rim groups' tables (dense_memo = 2): out[28] = their bytes (0: none built), out[29] =
+ * the memoised groups of fewer than 256 voxels of that pass; out[8] then counts 8 B of counts more per listed unit and no intensity lines for them. */
 int vrg_get_stats(vrg_handle* h, int64_t* out, int64_t cap);
 
 /* Diagnostic builds only (compiled with -DVRG_STAMPS, tools/chain_stamps.py): 64 in-kernel time stamps (100-MHz ticks) of
