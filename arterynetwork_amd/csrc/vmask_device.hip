@@ -32,6 +32,20 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int32_t EDT_INF = 1 << 29;
+// "No zero voxel on this line yet", per arithmetic width of the envelope pass (edt_squared chooses): above every real squared
+// distance of the width.  The 32-bit width serves volumes whose squared diagonal is below 2^29.  The wide one serves the rest,
+// where a real squared distance reaches 3 * 31999^2 = 3 071 808 003 (extents <= 32000): its values are UNSIGNED 32-bit numbers,
+// in G, in the packed stack entries and in what k_transpose12 / k_threshold read, and its sentinel is 2^32 - 1.
+constexpr uint32_t EDT_INF_WIDE = 0xffffffffu;
+template <typename I> struct EdtWidth;
+template <> struct EdtWidth<int32_t> {
+    static constexpr int32_t INF = EDT_INF;
+    static __device__ __forceinline__ int32_t ld(uint32_t g) { return (int32_t)g; }
+};
+template <> struct EdtWidth<long long> {
+    static constexpr long long INF = (long long)EDT_INF_WIDE;
+    static __device__ __forceinline__ long long ld(uint32_t g) { return (long long)g; }      // (zero-extended)
+};
 std::string g_err;
 
 #define VM_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return VRG_E_INTERNAL; } } while (0)
@@ -43,7 +57,7 @@ int grid_for(uint64_t n) { return (int)std::min<uint64_t>(65535u * 16u, (n + TPB
 // ---------------------------------------------------------------- EDT
 // phase 1: squared distance to the nearest zero voxel along axis 0; one thread per VEC neighbouring (i1,i2) columns (VEC = 4
 // when the row length allows aligned 4-voxel accesses: 256 B of mask and 1 KB of G per wave and row).  The downward scan
-// leaves its distance in F as 16 bits (65535 = no zero above; anything >= 32768 ends as EDT_INF anyway), the upward scan
+// leaves its distance in F as 16 bits (65535 = no zero above; anything >= 32768 - no extent is that long - ends as the sentinel `inf` anyway), the upward scan
 // reads that back - it is 0 exactly where the mask is, so the mask is not read again - and writes min(down, up)^2:
 // 9 bytes per voxel (round 3: 14), the loads of 32 / 16 rows in flight together (round 3: one row at a time, each waited for;
 // with 4 columns per thread a 880x880x640 volume has only ~2 waves per SIMD: the depth of the batches is what fills the bus).
@@ -55,7 +69,7 @@ template <int VEC> struct Ax0;
 template <> struct Ax0<1> { using M = uint8_t; using F = uint16_t; using G = int32_t; };
 template <> struct Ax0<4> { using M = uchar4; using F = ushort4; using G = int4; };
 template <int VEC>
-__global__ void __launch_bounds__(TPB) k_edt_axis0(const uint8_t* __restrict__ mask, uint16_t* __restrict__ F, int32_t* __restrict__ G, Dims d) {
+__global__ void __launch_bounds__(TPB) k_edt_axis0(const uint8_t* __restrict__ mask, uint16_t* __restrict__ F, int32_t* __restrict__ G, Dims d, uint32_t inf) {
     using MT = typename Ax0<VEC>::M; using FT = typename Ax0<VEC>::F; using GT = typename Ax0<VEC>::G;
     const uint32_t ncol = (uint32_t)d.n1 * (uint32_t)d.n2 / VEC;           // (columns in units of VEC)
     const MT* __restrict__ mk = reinterpret_cast<const MT*>(mask);
@@ -78,7 +92,7 @@ __global__ void __launch_bounds__(TPB) k_edt_axis0(const uint8_t* __restrict__ m
             for (int v = 0; v < VEC; v++) {
                 dist[v] = fb[v] ? min(dist[v] + 1u, 65535u) : 0u;
                 const uint32_t g = min((uint32_t)fb[v], dist[v]);
-                gb[v] = g >= 32768u ? EDT_INF : (int32_t)(g * g);
+                gb[v] = (int32_t)(g >= 32768u ? inf : g * g);
             }
             GT gv; __builtin_memcpy(&gv, gb, 4 * VEC);
             go[(size_t)i * ncol + col] = gv;
@@ -177,9 +191,10 @@ constexpr int EDT_CHUNK = EDT_CHUNK_N;
 constexpr int EDT_AHEAD = EDT_AHEAD_N;
 constexpr int EDT_TPB = EDT_TPB_N;
 __host__ __device__ inline uint32_t edt_chunks(int32_t n2) { return ((uint32_t)n2 + 63u) / 64u; }     // 64-line groups per i0 slab
-template <typename I>      // int32_t for volumes whose squared diagonal is below EDT_INF (edt_squared), else long long
+template <typename I>      // int32_t for volumes whose squared diagonal is below EDT_INF (edt_squared), else long long (EdtWidth: unsigned values)
 __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restrict__ Gin, int32_t* __restrict__ Gout, uint2* __restrict__ SP, Dims d) {
     __shared__ uint2 ring[EDT_RING][EDT_TPB];
+    using W = EdtWidth<I>;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t cpl = edt_chunks(d.n2), nitems = (uint32_t)d.n0 * cpl;
     const int32_t m = d.n1;
@@ -196,7 +211,7 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
         // entries [low, q] of the stack are in the ring (entry i in slot i % EDT_RING), entries [eb, low) in the spill
         // area (low - eb a multiple of EDT_CHUNK), entries [0, eb) are final and written: rows [0, ue) of the output
         int32_t q = 0, low = 0, eb = 0, ue = 0;
-        I ts = 0, tt = 0, tg = gin[AT(0)], tv = tg;      // top of the stack: site, start, G(site), its value at its start
+        I ts = 0, tt = 0, tg = W::ld((uint32_t)gin[AT(0)]), tv = tg;      // top of the stack: site, start, G(site), its value at its start
         I dn_t = 0, dn_v = 0;                            // while low > eb: start of entry eb + EDT_CHUNK (the one above the oldest spilled chunk) and its value there
         ring[0][tid] = make_uint2(0u, (uint32_t)tg);
         auto pop = [&]() {                                        // q was decremented and is >= eb: its entry becomes the top
@@ -209,12 +224,12 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
                 for (int i = 0; i < EDT_CHUNK; i++) ring[SLOT(low + i)][tid] = e[i];
             }
             const uint2 p = ring[SLOT(q)][tid];
-            ts = p.x & 0xffffu; tt = p.x >> 16; tg = (int32_t)p.y; tv = sq_add(tt - ts, tg);
+            ts = p.x & 0xffffu; tt = p.x >> 16; tg = W::ld(p.y); tv = sq_add(tt - ts, tg);
         };
         auto rows_out = [&](I s0, I g0, I r0, I r1) {             // rows [r0, r1) of the output from entry (site s0, G g0)
             for (I r = r0; r < r1; r++) {
                 const I v = sq_add(r - s0, g0);
-                gout[AT(r)] = v >= EDT_INF ? EDT_INF : (int32_t)v;
+                gout[AT(r)] = (int32_t)(uint32_t)(v >= W::INF ? W::INF : v);
             }
         };
         auto fetch = [&](int32_t (&gv)[EDT_AHEAD], int32_t u0) {  // the line's values of a batch (rows past the end repeat the last one)
@@ -236,22 +251,22 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
                 for (int i = 0; i < EDT_CHUNK; i++) e[i] = spill[eb + i];
 #pragma unroll
                 for (int i = 0; i < EDT_CHUNK; i++)
-                    rows_out(e[i].x & 0xffffu, (int32_t)e[i].y, e[i].x >> 16, i + 1 < EDT_CHUNK ? (I)(e[(i + 1) % EDT_CHUNK].x >> 16) : dn_t);
+                    rows_out(e[i].x & 0xffffu, W::ld(e[i].y), e[i].x >> 16, i + 1 < EDT_CHUNK ? (I)(e[(i + 1) % EDT_CHUNK].x >> 16) : dn_t);
                 ue = (int32_t)dn_t; eb += EDT_CHUNK;
                 if (low > eb) {                                   // the entry above the next chunk: spilled itself, or the bottom of the ring
                     const uint2 n = eb + EDT_CHUNK < low ? spill[eb + EDT_CHUNK] : ring[SLOT(low)][tid];
                     const I sn = n.x & 0xffffu;
-                    dn_t = n.x >> 16; dn_v = sq_add(dn_t - sn, (I)(int32_t)n.y);
+                    dn_t = n.x >> 16; dn_v = sq_add(dn_t - sn, W::ld(n.y));
                 }
             }
             if (low == eb && low < q) {                       // the final bottom of the stack leaves (nothing of it is in the spill area)
                 uint2 p0 = ring[SLOT(low)][tid];
                 for (;;) {
                     const uint2 p1 = ring[SLOT(low + 1)][tid];
-                    const I s1 = p1.x & 0xffffu, t1 = p1.x >> 16, v1 = sq_add(t1 - s1, (I)(int32_t)p1.y);
+                    const I s1 = p1.x & 0xffffu, t1 = p1.x >> 16, v1 = sq_add(t1 - s1, W::ld(p1.y));
                     const I dd = u0 - t1;
                     if (!(dd >= 0 && v1 <= mul_(dd, dd))) break;   // (else entry low + 1 can still be popped: entry low may become the top again)
-                    rows_out(p0.x & 0xffffu, (int32_t)p0.y, p0.x >> 16, t1);
+                    rows_out(p0.x & 0xffffu, W::ld(p0.y), p0.x >> 16, t1);
                     ue = (int32_t)t1; low++; eb++;
                     p0 = p1;
                     if (low >= q) break;
@@ -261,12 +276,12 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
             for (int k = 0; k < EDT_AHEAD; k++) {
                 const int32_t u = u0 + k;
                 if (u >= m) break;
-                const I Gu = gv[k];
+                const I Gu = W::ld((uint32_t)gv[k]);
                 while (q >= eb) {
                     if (tv <= sq_add(tt - u, Gu)) break;
                     if (--q >= eb) pop();
                 }
-                if (q < eb) { q = 0; low = 0; ts = u; tt = 0; tg = Gu; tv = sq_add((I)u, Gu); ring[0][tid] = make_uint2((uint32_t)u, (uint32_t)(int32_t)Gu); }   // (eb == 0: a final entry is never popped)
+                if (q < eb) { q = 0; low = 0; ts = u; tt = 0; tg = Gu; tv = sq_add((I)u, Gu); ring[0][tid] = make_uint2((uint32_t)u, (uint32_t)Gu); }   // (eb == 0: a final entry is never popped)
                 else {
                     const I w = 1 + floordiv(mul_((I)u + ts, (I)u - ts) + Gu - tg, (I)2 * (u - ts));
                     if (w < m) {                                  // w >= 1 here: the top still wins at its own start
@@ -278,11 +293,11 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
                             if (low - eb == EDT_CHUNK) {          // the first spilled chunk: the entry above it is the ring's bottom now
                                 const uint2 pn = ring[SLOT(low)][tid];
                                 const I sn = pn.x & 0xffffu;
-                                dn_t = pn.x >> 16; dn_v = sq_add(dn_t - sn, (I)(int32_t)pn.y);
+                                dn_t = pn.x >> 16; dn_v = sq_add(dn_t - sn, W::ld(pn.y));
                             }
                         }
                         ts = u; tt = w; tg = Gu; tv = sq_add(w - u, Gu);
-                        ring[SLOT(q)][tid] = make_uint2((uint32_t)u | ((uint32_t)w << 16), (uint32_t)(int32_t)Gu);
+                        ring[SLOT(q)][tid] = make_uint2((uint32_t)u | ((uint32_t)w << 16), (uint32_t)Gu);
                     }
                 }
             }
@@ -293,7 +308,7 @@ __global__ void __launch_bounds__(EDT_TPB) k_edt_envelope(const int32_t* __restr
         for (int32_t u0 = 1; u0 < m; u0 += EDT_AHEAD) { int32_t gv[EDT_AHEAD]; fetch(gv, u0); batch(u0, gv); }
         for (int32_t u = m - 1; u >= ue; u--) {
             const I v = sq_add(u - ts, tg);
-            gout[AT(u)] = v >= EDT_INF ? EDT_INF : (int32_t)v;
+            gout[AT(u)] = (int32_t)(uint32_t)(v >= W::INF ? W::INF : v);
             if (u == tt && --q >= eb) pop();
         }
 #undef AT
@@ -320,7 +335,7 @@ __global__ void __launch_bounds__(256) k_transpose12(const int32_t* __restrict__
         for (int j = ty; j < 64; j += 4) {
             int b = b0 + j, a = a0 + tx;
             if (a < na && b < nb) {
-                if constexpr (sizeof(OUT) == 8) out[slab + (size_t)b * na + a] = sqrt((double)tile[tx][j]);
+                if constexpr (sizeof(OUT) == 8) out[slab + (size_t)b * na + a] = sqrt((double)(uint32_t)tile[tx][j]);      // (unsigned: the wide width's values pass 2^31)
                 else out[slab + (size_t)b * na + a] = tile[tx][j];
             }
         }
@@ -341,11 +356,13 @@ int edt_squared(const uint8_t* dmask, Dims d, int32_t* G, double* dist = nullptr
     int32_t* G2 = nullptr; uint2* SP = nullptr;
     VM_TRY(hipMalloc(&G2, V * 4));
     if (hipMalloc(&SP, spill_entries * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(G2); g_err = "out of device memory (EDT scratch)"; return VRG_E_MEM; }
-    // (every finite squared distance, and so every square and sum of the envelope pass, below EDT_INF = 2^29)
+    // (every finite squared distance, and so every square and sum of the envelope pass, below EDT_INF = 2^29; otherwise the wide
+    // width: unsigned 32-bit values under the sentinel 2^32 - 1, 64-bit arithmetic)
     const bool small = (int64_t)d.n0 * d.n0 + (int64_t)d.n1 * d.n1 + (int64_t)d.n2 * d.n2 < (int64_t)EDT_INF;
+    const uint32_t inf = small ? (uint32_t)EDT_INF : EDT_INF_WIDE;
     // (G2 holds the downward scan's 16-bit distances first)
-    if (((size_t)d.n1 * d.n2) % 4 == 0 && (reinterpret_cast<uintptr_t>(dmask) & 3u) == 0) k_edt_axis0<4><<<grid_for((uint64_t)d.n1 * d.n2 / 4), TPB>>>(dmask, reinterpret_cast<uint16_t*>(G2), G, d);
-    else k_edt_axis0<1><<<grid_for((uint64_t)d.n1 * d.n2), TPB>>>(dmask, reinterpret_cast<uint16_t*>(G2), G, d);
+    if (((size_t)d.n1 * d.n2) % 4 == 0 && (reinterpret_cast<uintptr_t>(dmask) & 3u) == 0) k_edt_axis0<4><<<grid_for((uint64_t)d.n1 * d.n2 / 4), TPB>>>(dmask, reinterpret_cast<uint16_t*>(G2), G, d, inf);
+    else k_edt_axis0<1><<<grid_for((uint64_t)d.n1 * d.n2), TPB>>>(dmask, reinterpret_cast<uint16_t*>(G2), G, d, inf);
     auto egrid = [](Dims e) { return (int)std::min<uint64_t>(65535u * 16u, ((uint64_t)e.n0 * edt_chunks(e.n2) * 64u + EDT_TPB - 1) / EDT_TPB); };
     if (small) k_edt_envelope<int32_t><<<egrid(d), EDT_TPB>>>(G, G2, SP, d);
     else k_edt_envelope<long long><<<egrid(d), EDT_TPB>>>(G, G2, SP, d);
@@ -533,7 +550,7 @@ template <class T> __global__ void k_threshold(const T* __restrict__ v, const in
                                                uint8_t* __restrict__ fg, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         T x = v[i];
-        if (sqrt((double)G[i]) <= edt_max && x <= thr1) x = 0;     // :187-189
+        if (sqrt((double)(uint32_t)G[i]) <= edt_max && x <= thr1) x = 0;     // :187-189
         if (x <= thr2) x = 0;                                       // :190-191
         fg[i] = x != 0 ? 1 : 0;                                     // :194
     }

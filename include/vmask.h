@@ -88,7 +88,12 @@ extern "C" {
 #endif
 
 /* out[v] = Euclidean distance (unit sampling) from v to the nearest voxel with mask == 0; 0 where mask == 0.
- * mask: uint8.  out: float64, like scipy returns. */
+ * mask: uint8.  out: float64, like scipy returns: the correctly rounded root of the exact integer squared distance, for every
+ * shape that is accepted (extents <= 32000, fewer than 2^31 voxels), distances of sqrt(2^29) and more included.
+ * Inside, "no zero voxel on this line" is a sentinel above every real squared distance of the arithmetic width in use: 2^29
+ * where n0^2 + n1^2 + n2^2 < 2^29 (32-bit arithmetic), 2^32 - 1 otherwise (64-bit arithmetic on unsigned 32-bit values; a real
+ * squared distance is at most 3 * 31999^2 < 2^32).  A mask without any zero voxel has no distance transform: out is then the
+ * root of the sentinel everywhere, which is unspecified (scipy's answer for it is arbitrary too). */
 int vmask_edt(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, double* out);
 
 /* Connected components of volume != 0 with skimage's `connectivity` 1 (6), 2 (18) or 3 (26 neighbours).
