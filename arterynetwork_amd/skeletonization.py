@@ -410,11 +410,42 @@ def pathLengths(stepCounts, jumpOffset, spacing):
     return out + _norm3(jo[:, 1].astype(np.float64) * h)
 
 
+def interiorJumps(jumps, jumpOffset):
+    """Per branch, the pairs that are no 26-neighbours other than its first and its last pair: ``jumps`` less the front and the back pair
+    where ``jumpOffset`` is set (a branch of two entries has one pair, the front one).  f10's tables have none."""
+    jo = np.asarray(jumpOffset, np.int64).reshape(-1, 2, 3)
+    return np.asarray(jumps, np.int64) - (jo != 0).any(axis=2).sum(axis=1)
+
+
 def _angle(a, b):
     """The angle between the rows of a and b in degrees, from the clipped cosine."""
     with np.errstate(invalid='ignore', divide='ignore'):
         c = (a * b).sum(axis=-1) / (_norm3(a) * _norm3(b))
     return np.arccos(np.clip(c, -1.0, 1.0)) / np.pi * 180
+
+
+def _two_entry_radii(meanRadius, sigma, n, ends):
+    """A branch of two entries has no interior to sample: its ``meanRadius`` becomes what the reference gives it
+    (manualCorrectionGUI.py:315-334) and its ``sigma`` NaN, in place.  Per end: ``np.mean`` of the meanRadius of every other branch end
+    at that node whose branch has a value - the longer branches, and the two-entry branches of smaller index, which the reference
+    has handled by then - or 0 without one; then the mean of the two ends' values, or the one that is not 0, or 0."""
+    short = np.flatnonzero(n == 2)
+    if not len(short):
+        return
+    flat = ends.ravel()
+    by_node = np.argsort(flat, kind='stable')                             # the branch ends (2 b + e) grouped by node
+    nodes = flat[by_node]
+    known = n != 2
+    for b in short.tolist():
+        side = []
+        for v in ends[b].tolist():
+            there = by_node[np.searchsorted(nodes, v, 'left'):np.searchsorted(nodes, v, 'right')] >> 1 if v >= 0 else np.zeros(0, np.int64)
+            values = [float(meanRadius[k]) for k in there.tolist() if k != b and known[k]]
+            side.append(float(np.mean(values)) if values else 0.0)
+        head, tail = side
+        meanRadius[b] = (head + tail) / 2 if head != 0 and tail != 0 else head if head != 0 else tail
+        sigma[b] = np.nan
+        known[b] = True
 
 
 def deriveMorphometry(raw, offsets, branchEnds, nodeKind, spacing):
@@ -434,6 +465,7 @@ def deriveMorphometry(raw, offsets, branchEnds, nodeKind, spacing):
         out['voxelLength'] = n.astype(np.int64)
         out['meanRadius'] = raw['radiusSum'] / raw['radiusCount'].astype(np.float64)
         out['sigma'] = np.sqrt(raw['radiusDevSq'] / raw['radiusCount'].astype(np.float64))
+        _two_entry_radii(out['meanRadius'], out['sigma'], n, ends)
         out['aspectRatio'] = raw['pathLength'] / out['meanRadius']
     open_ = ends[:, 0] >= 0 if B else np.zeros(0, bool)
     terminating = np.zeros(B, bool)
@@ -516,7 +548,10 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     size per axis (default 1 1 1; positive, finite, max / min <= 1000), `roots` node indices or coordinate triples of node
     representatives (``ValueError`` when a triple is none), `localSteps` the reach of the local direction.  A host graph gives
     host arrays, a graph of tensors on the GPU gives tensors on the same device (the derived quantities are computed from host
-    copies of the B- and N-sized outputs and sent back).  `info`, when a dict, receives ``depthRounds`` and ``levelRounds``.
+    copies of the B- and N-sized outputs and sent back).  `info`, when a dict, receives ``depthRounds``, ``levelRounds`` and
+    ``interiorJumps``: the pairs of consecutive entries INSIDE a branch (not its first or last pair) that are no 26-neighbours.
+    `branchGraph` emits none; a table that has one is refused with a ``ValueError`` after the kernels have run, because
+    ``pathLength`` counts the two end pairs only and would come out short (the reference sums every pair).
 
     From the kernels, for a branch b of n entries (include/vmask.h has the summation order):
       stepCounts[b, c]   consecutive entry pairs of class c = 4 |d0| + 2 |d1| + |d2| - 1;  jumps[b]: pairs that are not 26-adjacent
@@ -536,8 +571,10 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     Derived here (`deriveMorphometry`):
       eculideanLength = |chord * spacing| (sic, the reference's spelling); tortuosity = pathLength / eculideanLength (inf for a closed
       branch); voxelLength = n; meanRadius = radiusSum / radiusCount; sigma = sqrt(radiusDevSq / radiusCount) (np.std's population
-      form); aspectRatio = pathLength / meanRadius; type: 0 terminating (an end is an end point), 1 bifurcating, -1 a closed curve
-      without a node (graphRelated.py:81-84).
+      form); a branch of TWO entries takes the reference's rule instead (`_two_entry_radii`: the mean over its two ends of the mean
+      meanRadius of the other branches there) and has sigma NaN, the raw radius outputs staying what the kernel sampled; aspectRatio =
+      pathLength / meanRadius; type: 0 terminating (an end is an end point), 1 bifurcating, -1 a closed curve without a node
+      (graphRelated.py:81-84).
     The bifurcation table covers the nodes with incident branches whose three branches have n >= 3 (bifurcationNode: node index;
     bifurcationBranches: child, child, parent).  The parent is the node's parentBranch when that is one of the three, the children
     then ascend by branch index; otherwise, with the unit local directions u0, u1, u2 in ascending branch index, the first maximum
@@ -601,6 +638,13 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     if R:
         raw.update(pathDistance=distance, parentBranch=depth[:, 0], depthLevel=depth[:, 1], depthVoxel=depth[:, 2], branchLevel=level)
     hraw = {k: np.ascontiguousarray(host(v)) for k, v in raw.items()}
+    interior = interiorJumps(hraw['jumps'], hraw['jumpOffset'])
+    if info is not None:
+        info['depthRounds'], info['levelRounds'], info['interiorJumps'] = int(counts[0]), int(counts[1]), int(interior.sum())
+    if interior.any():
+        k = int(np.flatnonzero(interior)[0])
+        raise ValueError('branch {} has {} pairs of consecutive entries inside it that are no 26-neighbours ({} such pairs in the table): pathLength leaves '
+                         'them out, so the table is refused'.format(k, int(interior[k]), int(interior.sum())))
     derived = deriveMorphometry(hraw, host(off), host(ends), host(graph.nodeKind), h)
     result = BranchMorphometry()
     for k in MORPHOMETRY_DEPTH:
@@ -610,8 +654,6 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     for k, v in derived.items():
         setattr(result, k, torch.as_tensor(v, device=tdev) if on_device else v)
     result.spacing, result.localSteps, result.roots, result.depthRounds = h, int(localSteps), root_ix, int(counts[0])
-    if info is not None:
-        info['depthRounds'], info['levelRounds'] = int(counts[0]), int(counts[1])
     return result
 
 
@@ -624,12 +666,13 @@ def writeMorphometry(graph, measured, baseFolder, parts=None):
     """The files of ``main(..., morphometry=True)`` for a host `BranchGraph` and its `BranchMorphometry`; returns their names.
     ``branchMorphometry.npz``: every array of ``measured.names()``, ``names``, ``spacing``, ``localSteps``, ``roots``.
     ``graphRepresentationWithEdgeInfo.graphml``: the graph of `writeGraphml` with the edge attributes pathLength, eculideanLength,
-    tortuosity, voxelLength, meanRadius, sigma and segmentIndex of the edge's branch, the node attribute radius at every voxel of a
+    tortuosity, voxelLength, meanRadius, sigma (not for a branch of two entries) and segmentIndex of the edge's branch, the node attribute radius at every voxel of a
     branch, and depthVoxel / depthLevel / pathDistance at the reached node representatives.
     ``segmentInfoDict.pkl`` (keyed by branch index, closed branches left out as graphRelated.py:64 does) and ``nodeInfoDict.pkl``
     (keyed by coordinate tuple: every node representative) with the reference's key names and plain Python values, pickle
-    protocol 2.  With `parts` (a `Compartments` of host arrays) the entries of owned branches and nodes gain ``partitionName``, and
-    the segments ``segmentLevel`` - the partition's, as graphRelated.py:72-74,108-110 reads them."""
+    protocol 2: per entry the keys that `calculateProperty` writes and no others - a branch of two entries has no ``sigma``, and
+    ``segmentLevel`` comes from a partition alone.  With `parts` (a `Compartments` of host arrays) the entries of owned branches and
+    nodes gain ``partitionName``, and the segments ``segmentLevel`` - the partition's, as graphRelated.py:72-74,108-110 reads them."""
     import pickle
     m = measured
     names = m.names()
@@ -672,7 +715,8 @@ def writeMorphometry(graph, measured, baseFolder, parts=None):
         for (a, b), k in edges.items():
             f.write('    <edge source="{}" target="{}">\n      <data key="d0">{}</data>\n'.format(a, b, k))
             for i, col in enumerate(columns):
-                f.write('      <data key="d{}">{!r}</data>\n'.format(i + 1, col[k]))
+                if edge_keys[i] != 'sigma' or off[k + 1] - off[k] != 2:
+                    f.write('      <data key="d{}">{!r}</data>\n'.format(i + 1, col[k]))
             f.write('    </edge>\n')
         f.write('  </graph>\n</graphml>\n')
     ends = np.asarray(graph.branchEnds, np.int64).reshape(-1, 2)
@@ -680,11 +724,9 @@ def writeMorphometry(graph, measured, baseFolder, parts=None):
     for k in range(B):
         if ends[k, 0] < 0 or (ends[k, 0] == ends[k, 1]):                  # (same head and tail)
             continue
-        d = {key: col[k] for key, col in zip(edge_keys, columns)}
+        d = {key: col[k] for key, col in zip(edge_keys, columns) if key != 'sigma' or off[k + 1] - off[k] != 2}      # (no sigma for two entries)
         d['aspectRatio'] = float(m.aspectRatio[k])
         d['type'] = 'terminating' if m.type[k] == 0 else 'bifurcating'
-        if reached and m.branchLevel[k] >= 0:
-            d['segmentLevel'] = int(m.branchLevel[k])
         if not np.isnan(m.localBifurcationTorque[k]):
             d['localBifurcationTorque'] = float(m.localBifurcationTorque[k])
         if parts is not None and parts.branchCompartment[k]:

@@ -534,7 +534,10 @@ def _content(path):
         return gzip.decompress(raw)
     if path.name.endswith('.npz'):
         with np.load(str(path), allow_pickle=True) as z:
-            return {k: (z[k].dtype.str, z[k].shape, z[k].tobytes() if z[k].dtype != object else z[k].tolist()) for k in z.files}
+            arrays = {k: z[k] for k in z.files}
+        if 'countNames' in arrays:                                        # (branchGraph.npz: labelRounds describes the run and differs between two)
+            arrays['counts'] = arrays['counts'][arrays['countNames'] != 'labelRounds']
+        return {k: (a.dtype.str, a.shape, a.tobytes() if a.dtype != object else a.tolist()) for k, a in arrays.items()}
     return raw
 
 

@@ -374,7 +374,8 @@ def _volume_case(density, seed):
     import test_morphometry as TMo
     t = TMo._of_volume(TMo.TB._random((24, 24, 24), density, seed))
     m = S.branchMorphometry(t.graph(), dist=TMo._dist_for(t.shape))
-    R = F.branchResistance(np.maximum(m.pathLength, 0.5) * 0.5e-3, m.meanRadius * 0.5e-3, c=120.0)
+    # (a two-entry branch takes its meanRadius from its neighbours, as in the reference: 0 where none has one - floored like the length)
+    R = F.branchResistance(np.maximum(m.pathLength, 0.5) * 0.5e-3, np.maximum(m.meanRadius, 0.5) * 0.5e-3, c=120.0)
     fixed = (t.degree == 1).astype(np.uint8)
     if not fixed.any():                                                    # (the densest volume is one cluster with two loops)
         fixed[0] = 1

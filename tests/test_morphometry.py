@@ -598,6 +598,13 @@ def test_main_writes_the_files(tmp_path, capsys):
     new = ['branchMorphometry.npz', 'graphRepresentationWithEdgeInfo.graphml', 'nodeInfoDict.pkl', 'segmentInfoDict.pkl']
     assert sorted(os.listdir(str(measured))) == sorted(os.listdir(str(plain)) + new)
     for name in os.listdir(str(plain)):                                   # every other file byte for byte
+        if name == S.BRANCH_FILE:                                         # (but for labelRounds, which describes the run and differs between two)
+            with np.load(str(plain / name)) as x, np.load(str(measured / name)) as y:
+                assert x.files == y.files
+                for k in x.files:
+                    keep = x['countNames'] != 'labelRounds' if k == 'counts' else slice(None)
+                    assert x[k].dtype == y[k].dtype and np.array_equal(x[k][keep], y[k][keep]), (name, k)
+            continue
         assert (plain / name).read_bytes() == (measured / name).read_bytes(), name
     for name in new:
         assert '{} saved to {}.'.format(name, os.path.join(str(measured), name)) in said
@@ -619,7 +626,8 @@ def test_main_writes_the_files(tmp_path, capsys):
     keep = [k for k in range(B) if graph.branchEnds[k, 0] >= 0 and graph.branchEnds[k, 0] != graph.branchEnds[k, 1]]
     assert sorted(seg) == keep and len(keep) > 0
     for k, d in seg.items():
-        assert {'pathLength', 'eculideanLength', 'tortuosity', 'voxelLength', 'meanRadius', 'sigma', 'type', 'aspectRatio'} <= set(d)
+        assert {'pathLength', 'eculideanLength', 'tortuosity', 'voxelLength', 'meanRadius', 'type', 'aspectRatio'} <= set(d)
+        assert ('sigma' in d) == (d['voxelLength'] != 2) and 'segmentLevel' not in d      # (two entries: the reference's rule, no sigma; a level comes from a partition)
         assert all(type(x) in (float, int, str) for x in d.values()) and d['type'] in ('terminating', 'bifurcating')
         assert d['pathLength'] == want.pathLength[k] and d['voxelLength'] == want.voxelLength[k] and d['meanRadius'] == want.meanRadius[k]
     assert sorted(node) == sorted(tuple(c) for c in graph.nodeCoords.tolist())
@@ -647,7 +655,7 @@ def test_main_writes_the_files(tmp_path, capsys):
     for a, b, d in G.edges(data=True):
         k = d['segmentIndex']
         assert d['pathLength'] == want.pathLength[k] and d['voxelLength'] == want.voxelLength[k] and d['meanRadius'] == want.meanRadius[k]
-        assert {'eculideanLength', 'tortuosity', 'sigma'} <= set(d)
+        assert {'eculideanLength', 'tortuosity'} <= set(d) and ('sigma' in d) == (d['voxelLength'] != 2)
     for v in np.flatnonzero(want.depthLevel >= 0).tolist():
         a = str(tuple(graph.nodeCoords[v].tolist()))
         assert G.nodes[a]['depthLevel'] == want.depthLevel[v] and G.nodes[a]['depthVoxel'] == want.depthVoxel[v] and G.nodes[a]['pathDistance'] == want.pathDistance[v]
