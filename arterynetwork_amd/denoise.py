@@ -118,8 +118,9 @@ def medianFilter(volume, radius=1, device=0):
     return out
 
 
-def main(baseFolder=None, method='diffusion', outputName=DENOISED_FILE, **parameters):
-    """File-level step in front of ``vesselness.main``: ``brainVolume.nii.gz`` denoised by `method` 'diffusion'
+def main(baseFolder=None, method='diffusion', outputName=DENOISED_FILE, volumeName=BRAIN_FILE, **parameters):
+    """File-level step in front of ``vesselness.main``: `volumeName` (``brainVolume.nii.gz``; the output of ``bias.main`` behind
+    a bias-field correction) denoised by `method` 'diffusion'
     (``anisotropicDiffusion``; `parameters` must name `conductance`; the spacing is the norms of the affine's columns) or
     'median' (``medianFilter``), written as float32 `outputName` with the input's affine into the same folder.  Feed it on with
     ``vesselness.main(baseFolder, volumeName=outputName)``.  Returns the denoised volume."""
@@ -127,7 +128,7 @@ def main(baseFolder=None, method='diffusion', outputName=DENOISED_FILE, **parame
         raise ValueError("method: 'diffusion' or 'median'")
     if baseFolder is None:
         baseFolder = os.getcwd()
-    volume, affine = loadVolume(baseFolder, BRAIN_FILE)
+    volume, affine = loadVolume(baseFolder, volumeName)
     if method == 'diffusion':
         spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
         result = anisotropicDiffusion(volume, spacing=spacing, **parameters)

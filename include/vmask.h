@@ -74,6 +74,15 @@
  *   vmask_median       the median over a window of at most 3 x 3 x 3 voxels, scipy.ndimage.median_filter(mode='nearest'); it
  *                      keeps the value set of integer data.  Claimed: equality with scipy as numbers.  Not claimed: wider
  *                      windows.
+ *   vmask_bias_*       the "MR image bias field correction" step that the reference's README (Pre-processing) leaves to an external
+ *                      tool, in front of vmask_diffuse: an N4-style estimate by the definition below - log domain, histogram
+ *                      sharpening by Wiener deconvolution, an incremental cubic B-spline fit of the residual over a lattice
+ *                      that doubles per level; DESIGN.md section 9, f15.  Claimed: bit equality of the fit, the evaluation and
+ *                      the whole loop (field, trace and iteration counts) with the numpy restatement tests/bias_model.py, the
+ *                      model taking its sharpening map from vmask_bias_sharpen; that map within a measured rounding distance of
+ *                      an np.fft restatement; the corrected volume and the field within a measured distance of the model (the
+ *                      device's log and exp); bit-identical repeats.  Not claimed: agreement with ITK / Slicer (their
+ *                      linear-weight histogram, shrink factor, lattice refinement and convergence measure all differ).
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -426,6 +435,72 @@ int vmask_diffuse(int device, const void* volume, int dtype, int64_t n0, int64_t
  * VRG_E_ARG, before anything is written: a radius outside {0, 1}; a dtype other than the two; a null pointer; a shape outside
  * the envelope of the other passes.  VRG_E_MEM: the input and the output do not fit the device; everything allocated is freed. */
 int vmask_median(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, int r0, int r1, int r2, void* out);
+
+/* N4-style bias-field correction, by a definition of our own.  All arithmetic is float64, EVERY OPERATION ONE IEEE DOUBLE OPERATION
+ * IN THE WRITTEN ASSOCIATION, nothing contracted into an FMA; no float atomics (integer atomics count the histogram).
+ *
+ * Axis tables (host, double).  An axis of extent n with M spans has K = M + 3 control points.  For voxel index i:
+ *     u = ((i + 0.5) * M) / n;  s = min(floor(u), M - 1);  t = u - s;  o = 1.0 - t;
+ *     w0 = ((o*o)*o)/6.0;  w1 = ((((3.0*t - 6.0)*t)*t) + 4.0)/6.0;  w2 = (((((-3.0*t + 3.0)*t + 3.0)*t)) + 1.0)/6.0;  w3 = ((t*t)*t)/6.0;
+ *     S = ((w0*w0 + w1*w1) + w2*w2) + w3*w3;  c2_j = w_j*w_j;  c3_j = ((w_j*w_j)*w_j)/S.
+ * vmask_bias_axis_table writes them: s[n] and w, c2, c3 as [n][4].  Host code only.  VRG_E_ARG: n outside 1..32000, spans outside
+ * 1..64, a null pointer. */
+int vmask_bias_axis_table(int n, int spans, int32_t* s, double* w, double* c2, double* c3);
+
+/* The fit: the multilevel-B-spline approximation of Lee, Wolberg and Shin of the residual r (float64) over the voxels with
+ * mask != 0 (uint8), on a voxel grid, where it factorises into three contractions, each summed in ascending voxel index from +0.0:
+ *     N0[k0,y,z] = sum_x c3_0[x][k0 - s0[x]] * r[x,y,z],   D0[k0,y,z] = sum_x c2_0[x][k0 - s0[x]]
+ *                  over the x with s0[x] <= k0 <= s0[x] + 3 and mask[x,y,z] != 0 (what r holds elsewhere does not matter);
+ *     N1[k0,k1,z] = sum_y c3_1[y][k1 - s1[y]] * N0[k0,y,z], D1[k0,k1,z] = sum_y c2_1[y][k1 - s1[y]] * D0[k0,y,z]
+ *                  over the y with s1[y] <= k1 <= s1[y] + 3;  axis 2 likewise, giving N2 and D2 over (k0, k1, k2);
+ *     phi = N2 / D2 where D2 > 0, else 0.0.
+ * spans: the three M_a, each 1..64.  phi: float64 [M_0 + 3][M_1 + 3][M_2 + 3].  An empty mask gives phi = 0.
+ * VRG_E_ARG, before anything is written: spans outside 1..64, a null pointer, a shape outside the envelope of the other passes.
+ * VRG_E_MEM: r and the mask where they are host arrays and 2 (M_0 + 3) n1 n2 doubles do not fit the device; everything is freed. */
+int vmask_bias_fit(int device, const double* r, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, const int* spans, double* phi);
+
+/* The evaluation of a lattice phi [K0][K1][K2] on the voxel grid: three expansions, each a four-term sum over j = 0..3 ascending
+ * from +0.0:
+ *     E2[k0,k1,z] = sum_j w2[z][j] * phi[k0,k1,s2[z] + j];  E1[k0,y,z] = sum_j w1[y][j] * E2[k0,s1[y] + j,z];
+ *     F[x,y,z] = sum_j w0[x][j] * E1[s0[x] + j,y,z].
+ * out: float64 [n0][n1][n2].  Errors as vmask_bias_fit. */
+int vmask_bias_eval(int device, const double* phi, const int* spans, int64_t n0, int64_t n1, int64_t n2, double* out);
+
+/* The sharpening map.  Host code only: it touches no device.  counts: nb bin counts (float64), bin centres umin + k h,
+ * h = (umax - umin) / (nb - 1).  The counts are zero-padded to P = 512 at offset (P - nb) / 2; G is a Gaussian of
+ * sigma = fwhm / (2 sqrt(2 ln 2)) / h bins on the circular index min(k, P - k), normalised to sum 1.  With G^ and V^ the DFTs:
+ *     U = max(Re IDFT(conj(G^) / (|G^|^2 + noise) . V^), 0);  num = Re IDFT(G^ . DFT(centre . U));  den = Re IDFT(G^ . DFT(U));
+ *     E[k] = num / den where den > 1e-12 max(den), else the bin centre - cut back to the nb bins.
+ * The transforms are direct O(P^2) sums in double: E is a pure function of the inputs on one machine, and equals an FFT
+ * restatement up to rounding.  VRG_E_ARG: nb outside 8..256; fwhm or noise not finite and positive; umin, umax not finite or
+ * umax <= umin; a null pointer. */
+int vmask_bias_sharpen(const double* counts, int nb, double umin, double umax, double fwhm, double noise, double* E /* nb */);
+
+/* The loop.  v: float64 log intensities (finite over the mask); mask: uint8; m0: the spans of the first level.  b = 0.  Per level
+ * L = 0 .. levels - 1 the spans are M_a = m0_a 2^L; per iteration, at most `iterations` per level:
+ *   1. u = v - b over the mask; umin, umax its exact extrema.  umin == umax ends the whole run.
+ *   2. h = (umax - umin) / (nb - 1); counts (64-bit integers) at idx = clamp(floor((u - umin) / h + 0.5), 0, nb - 1); E from
+ *      vmask_bias_sharpen.
+ *   3. p = (u - umin) / h; i0 = clamp(floor(p), 0, nb - 2); f = p - i0; r = u - (E[i0] + f * (E[i0 + 1] - E[i0])) over the mask.
+ *   4. phi = fit(r, mask); b <- b + eval(phi) over the whole volume.
+ *   5. phi goes to the host; max |phi| < threshold ends the level.
+ * b: float64 [n0][n1][n2].  trace (may be NULL): one record of four doubles per iteration - level, max |phi|, umin, umax -, room
+ * for levels * iterations records; ntrace (may be NULL): their number.  Both are host pointers.
+ * VRG_E_ARG, before anything is written: m0 outside 1..32 or m0 2^(levels - 1) > 64; levels outside 1..6; iterations outside
+ * 1..200; nb outside 8..256; fwhm, noise or threshold not finite and positive; a null pointer; a shape outside the envelope of
+ * the other passes; an empty mask.  VRG_E_MEM: v, the mask and b where they are host arrays, one float64 work volume and the
+ * fit's 2 (M_0 + 3) n1 n2 doubles do not fit the device (volumes are not processed in slabs); everything allocated is freed. */
+int vmask_bias_log_field(int device, const double* v, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, const int* m0, int levels,
+                         int iterations, double threshold, int nb, double fwhm, double noise, double* b,
+                         double* trace /* may be NULL */, int64_t* ntrace /* may be NULL */);
+
+/* The correction of a volume I (VRG_F32 or VRG_F64).  mask (uint8) may be NULL: I > 0; a mask voxel with I <= 0 is taken out of the
+ * mask.  v = log((double) I) on the device over the mask; the loop; field = exp(b) and corrected = (double) I / field over the
+ * whole volume, both float64; field may be NULL.  The result depends on the device's log and exp.  Errors as
+ * vmask_bias_log_field, and a dtype other than the two. */
+int vmask_bias_correct(int device, const void* volume, int dtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
+                       const int* m0, int levels, int iterations, double threshold, int nb, double fwhm, double noise,
+                       double* corrected, double* field /* may be NULL */, double* trace /* may be NULL */, int64_t* ntrace /* may be NULL */);
 
 const char* vmask_last_error(void);
 
