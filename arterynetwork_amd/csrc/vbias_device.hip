@@ -25,6 +25,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 #pragma clang fp contract(off)
 
@@ -35,8 +36,6 @@ constexpr int EZ = 32;                           // k_bias_expand0: the planes o
 constexpr int GRID = 4096;                         // the grid-stride passes
 constexpr int PADDED = 512;                        // the transform length of the sharpening map
 constexpr int MAXBINS = 256;
-
-#define VB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 // ---------------------------------------------------------------- axis tables (host, double)
 struct AxisHost {
@@ -252,40 +251,27 @@ __global__ void __launch_bounds__(BT) k_bias_exp(const T* __restrict__ I, const 
 }
 
 // ---------------------------------------------------------------- host
-struct Pool {
-    std::vector<void*> p;
-    bool oom = false;
-    template <class T> T* get(size_t count) {
-        void* q = nullptr;
-        if (oom) return nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
-        p.push_back(q);
-        return (T*)q;
-    }
-    ~Pool() { for (void* q : p) (void)hipFree(q); }
-};
-
 int stream_grid(int64_t V) { return (int)std::min<int64_t>((V + BT - 1) / BT, GRID); }
 
-// the tables of one axis on the device: one allocation of the pool each
+// the tables of one axis on the device: one allocation each
 struct AxisSet {
     AxisHost host[3];
     AxisDev dev[3];
     int32_t* ds[3] = {};
     double* dw[3] = {};
-    bool alloc(Pool& pool, const int64_t* n) {
-        for (int a = 0; a < 3; a++) { ds[a] = pool.get<int32_t>((size_t)n[a]); dw[a] = pool.get<double>(12 * (size_t)n[a]); }
-        return !pool.oom;
+    int alloc(DevMem& mem, const int64_t* n) {
+        for (int a = 0; a < 3; a++) { VMASK_GRAB(ds[a], (size_t)n[a], "axis tables"); VMASK_GRAB(dw[a], 12 * (size_t)n[a], "axis tables"); }
+        return VRG_OK;
     }
     int set(const int64_t* n, const int* M) {
         for (int a = 0; a < 3; a++) {
             AxisHost& t = host[a];
             build_axis((int)n[a], M[a], t);
             const size_t c = 4 * (size_t)n[a];
-            VB_TRY(hipMemcpy(ds[a], t.s.data(), (size_t)n[a] * 4, hipMemcpyHostToDevice));
-            VB_TRY(hipMemcpy(dw[a], t.w.data(), c * 8, hipMemcpyHostToDevice));
-            VB_TRY(hipMemcpy(dw[a] + c, t.c2.data(), c * 8, hipMemcpyHostToDevice));
-            VB_TRY(hipMemcpy(dw[a] + 2 * c, t.c3.data(), c * 8, hipMemcpyHostToDevice));
+            VMASK_TRY(hipMemcpy(ds[a], t.s.data(), (size_t)n[a] * 4, hipMemcpyHostToDevice));
+            VMASK_TRY(hipMemcpy(dw[a], t.w.data(), c * 8, hipMemcpyHostToDevice));
+            VMASK_TRY(hipMemcpy(dw[a] + c, t.c2.data(), c * 8, hipMemcpyHostToDevice));
+            VMASK_TRY(hipMemcpy(dw[a] + 2 * c, t.c3.data(), c * 8, hipMemcpyHostToDevice));
             dev[a] = AxisDev{ds[a], dw[a], dw[a] + c, dw[a] + 2 * c, (int)n[a], t.K};
         }
         return VRG_OK;
@@ -295,13 +281,13 @@ struct AxisSet {
 // the work space of fit and eval at the largest lattice of a call: A holds [K0][n1][n2] (twice for the fit), B [K0][K1][n2]
 struct Lattice {
     double *An = nullptr, *Ad = nullptr, *Bn = nullptr, *Bd = nullptr, *phi = nullptr;
-    bool alloc(Pool& pool, const int64_t* n, const int* Mmax, bool fit) {
+    int alloc(DevMem& mem, const int64_t* n, const int* Mmax, bool fit) {
         const size_t K0 = Mmax[0] + 3, K1 = Mmax[1] + 3, K2 = Mmax[2] + 3;
-        An = pool.get<double>(K0 * n[1] * n[2]);
-        Bn = pool.get<double>(K0 * K1 * n[2]);
-        if (fit) { Ad = pool.get<double>(K0 * n[1] * n[2]); Bd = pool.get<double>(K0 * K1 * n[2]); }
-        phi = pool.get<double>(K0 * K1 * K2);
-        return !pool.oom;
+        VMASK_GRAB(An, K0 * n[1] * n[2], "lattice work space");
+        VMASK_GRAB(Bn, K0 * K1 * n[2], "lattice work space");
+        if (fit) { VMASK_GRAB(Ad, K0 * n[1] * n[2], "lattice work space"); VMASK_GRAB(Bd, K0 * K1 * n[2], "lattice work space"); }
+        VMASK_GRAB(phi, K0 * K1 * K2, "lattice");
+        return VRG_OK;
     }
 };
 
@@ -345,20 +331,20 @@ int check_loop(const int* m0, int levels, int iterations, double threshold, int 
 }
 
 // the loop on device-resident v, m and b (b is zeroed here); r is a float64 work volume
-int run_loop(const double* v, const uint8_t* m, const int64_t* n, const LoopArgs& a, double* b, double* r, Pool& pool, double* trace, int64_t* ntrace) {
+int run_loop(const double* v, const uint8_t* m, const int64_t* n, const LoopArgs& a, double* b, double* r, DevMem& mem, double* trace, int64_t* ntrace) {
     const int64_t V = n[0] * n[1] * n[2];
     const int g = stream_grid(V);
     int Mmax[3];
     for (int k = 0; k < 3; k++) Mmax[k] = a.m0[k] << (a.levels - 1);
     AxisSet ax;
     Lattice L;
-    ax.alloc(pool, n);
-    L.alloc(pool, n, Mmax, true);
-    double* part = pool.get<double>(2 * (size_t)GRID);
-    unsigned long long* dcounts = pool.get<unsigned long long>(MAXBINS);
-    double* dE = pool.get<double>(MAXBINS);
-    if (pool.oom) { vmask::set_error("out of device memory (bias field: the log volume, the field, the residual, the mask and 2 (m0 2^(levels-1) + 3) n1 n2 doubles of the fit; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    VB_TRY(hipMemset(b, 0, (size_t)V * 8));
+    double* part = nullptr; unsigned long long* dcounts = nullptr; double* dE = nullptr;
+    if (ax.alloc(mem, n) || L.alloc(mem, n, Mmax, true) || mem.grab(&part, 2 * (size_t)GRID, "partial extrema") ||
+        mem.grab(&dcounts, MAXBINS, "histogram") || mem.grab(&dE, MAXBINS, "sharpening map")) {
+        vmask::set_error("out of device memory (bias field: the log volume, the field, the residual, the mask and 2 (m0 2^(levels-1) + 3) n1 n2 doubles of the fit; volumes are not processed in slabs)");
+        return VRG_E_MEM;
+    }
+    VMASK_TRY(hipMemset(b, 0, (size_t)V * 8));
     std::vector<double> hpart(2 * (size_t)g), hist(a.nb), E(a.nb), hphi;
     std::vector<unsigned long long> hcounts(a.nb);
     int64_t records = 0;
@@ -372,24 +358,24 @@ int run_loop(const double* v, const uint8_t* m, const int64_t* n, const LoopArgs
         hphi.resize(nphi);
         for (int it = 0; it < a.iterations; it++) {
             k_bias_minmax<<<g, BT>>>(v, b, m, V, part);
-            VB_TRY(hipMemcpy(hpart.data(), part, hpart.size() * 8, hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(hpart.data(), part, hpart.size() * 8, hipMemcpyDeviceToHost));
             double umin = INFINITY, umax = -INFINITY;
             for (int k = 0; k < g; k++) { umin = std::fmin(umin, hpart[2 * k]); umax = std::fmax(umax, hpart[2 * k + 1]); }
             if (umin == umax) { stop = true; break; }
             if (!(std::isfinite(umin) && std::isfinite(umax))) { vmask::set_error("bias: the log intensities over the mask must be finite"); return VRG_E_ARG; }
             const double h = (umax - umin) / (double)(a.nb - 1);
-            VB_TRY(hipMemset(dcounts, 0, a.nb * sizeof(unsigned long long)));
+            VMASK_TRY(hipMemset(dcounts, 0, a.nb * sizeof(unsigned long long)));
             k_bias_hist<<<g, BT>>>(v, b, m, V, umin, h, a.nb, dcounts);
-            VB_TRY(hipMemcpy(hcounts.data(), dcounts, a.nb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(hcounts.data(), dcounts, a.nb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             for (int k = 0; k < a.nb; k++) hist[k] = (double)hcounts[k];
             const int src = vmask_bias_sharpen(hist.data(), a.nb, umin, umax, a.fwhm, a.noise, E.data());
             if (src) return src;
-            VB_TRY(hipMemcpy(dE, E.data(), a.nb * 8, hipMemcpyHostToDevice));
+            VMASK_TRY(hipMemcpy(dE, E.data(), a.nb * 8, hipMemcpyHostToDevice));
             k_bias_residual<<<g, BT>>>(v, b, m, V, umin, h, a.nb, dE, r);
             launch_fit(r, m, n, ax, L);
             launch_eval(n, ax, L, b, true);
-            VB_TRY(hipGetLastError());
-            VB_TRY(hipMemcpy(hphi.data(), L.phi, nphi * 8, hipMemcpyDeviceToHost));
+            VMASK_TRY(hipGetLastError());
+            VMASK_TRY(hipMemcpy(hphi.data(), L.phi, nphi * 8, hipMemcpyDeviceToHost));
             double top = 0.0;
             for (size_t k = 0; k < nphi; k++) top = std::fmax(top, std::fabs(hphi[k]));
             if (trace) { double* t = trace + 4 * records; t[0] = (double)level; t[1] = top; t[2] = umin; t[3] = umax; }
@@ -397,7 +383,7 @@ int run_loop(const double* v, const uint8_t* m, const int64_t* n, const LoopArgs
             if (top < a.threshold) break;
         }
     }
-    VB_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipDeviceSynchronize());
     if (ntrace) *ntrace = records;
     return VRG_OK;
 }
@@ -405,35 +391,35 @@ int run_loop(const double* v, const uint8_t* m, const int64_t* n, const LoopArgs
 template <class T>
 int correct(const T* volume, const uint8_t* mask, const int64_t* n, const LoopArgs& a, double* corrected, double* field, double* trace, int64_t* ntrace) {
     const size_t V = (size_t)n[0] * n[1] * n[2];
-    Pool pool;
-    const T* dI = volume; const uint8_t* dmask = mask; double* dcor = corrected; double* dfield = field;
+    DevMem mem;
     const bool in_host = !vmask::is_device_pointer(volume), mask_host = mask && !vmask::is_device_pointer(mask);
     const bool cor_host = !vmask::is_device_pointer(corrected), field_host = field && !vmask::is_device_pointer(field);
-    if (in_host) dI = pool.get<T>(V);
-    if (mask_host) dmask = pool.get<uint8_t>(V);
-    if (cor_host) dcor = pool.get<double>(V);
-    if (field_host) dfield = pool.get<double>(V);
-    double* v = pool.get<double>(V);
-    double* b = pool.get<double>(V);
-    uint8_t* m = pool.get<uint8_t>(V);
-    unsigned long long* total = pool.get<unsigned long long>(1);
-    if (pool.oom) { vmask::set_error("out of device memory (bias correction: the input, the outputs, three float64 volumes and the mask; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    if (in_host) VB_TRY(hipMemcpy((void*)dI, volume, V * sizeof(T), hipMemcpyHostToDevice));
-    if (mask_host) VB_TRY(hipMemcpy((void*)dmask, mask, V, hipMemcpyHostToDevice));
-    VB_TRY(hipMemset(total, 0, sizeof(unsigned long long)));
+    T* own_in = nullptr; uint8_t* own_mask = nullptr; double* own_cor = nullptr; double* own_field = nullptr;
+    double* v = nullptr; double* b = nullptr; uint8_t* m = nullptr; unsigned long long* total = nullptr;
+    if ((in_host && mem.grab(&own_in, V, "input")) || (mask_host && mem.grab(&own_mask, V, "mask")) || (cor_host && mem.grab(&own_cor, V, "corrected")) ||
+        (field_host && mem.grab(&own_field, V, "field")) || mem.grab(&v, V, "log volume") || mem.grab(&b, V, "log field") || mem.grab(&m, V, "mask") ||
+        mem.grab(&total, 1, "counter")) {
+        vmask::set_error("out of device memory (bias correction: the input, the outputs, three float64 volumes and the mask; volumes are not processed in slabs)");
+        return VRG_E_MEM;
+    }
+    const T* dI = in_host ? own_in : volume; const uint8_t* dmask = mask_host ? own_mask : mask;
+    double* dcor = cor_host ? own_cor : corrected; double* dfield = field_host ? own_field : field;
+    if (in_host) VMASK_TRY(hipMemcpy(own_in, volume, V * sizeof(T), hipMemcpyHostToDevice));
+    if (mask_host) VMASK_TRY(hipMemcpy(own_mask, mask, V, hipMemcpyHostToDevice));
+    VMASK_TRY(hipMemset(total, 0, sizeof(unsigned long long)));
     const int g = stream_grid((int64_t)V);
     k_bias_log<T><<<g, BT>>>(dI, dmask, (int64_t)V, v, m, total);
     unsigned long long inside = 0;
-    VB_TRY(hipMemcpy(&inside, total, sizeof inside, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&inside, total, sizeof inside, hipMemcpyDeviceToHost));
     if (!inside) { vmask::set_error("bias: the mask is empty (no voxel of it has a positive intensity)"); return VRG_E_ARG; }
     // the corrected volume is not needed until the end: it is the residual's work volume
-    const int rc = run_loop(v, m, n, a, b, dcor, pool, trace, ntrace);
+    const int rc = run_loop(v, m, n, a, b, dcor, mem, trace, ntrace);
     if (rc) return rc;
     k_bias_exp<T><<<g, BT>>>(dI, b, (int64_t)V, dcor, dfield);
-    VB_TRY(hipGetLastError());
-    VB_TRY(hipDeviceSynchronize());
-    if (cor_host) VB_TRY(hipMemcpy(corrected, dcor, V * 8, hipMemcpyDeviceToHost));
-    if (field_host) VB_TRY(hipMemcpy(field, dfield, V * 8, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    if (cor_host) VMASK_TRY(hipMemcpy(corrected, dcor, V * 8, hipMemcpyDeviceToHost));
+    if (field_host) VMASK_TRY(hipMemcpy(field, dfield, V * 8, hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 
@@ -513,24 +499,24 @@ extern "C" int vmask_bias_fit(int device, const double* r, const uint8_t* mask, 
     if (rc) return rc;
     const int64_t n[3] = {n0, n1, n2};
     const size_t V = (size_t)n0 * n1 * n2;
-    Pool pool;
+    DevMem mem;
     AxisSet ax;
     Lattice L;
-    const double* dr = r; const uint8_t* dm = mask;
     const bool r_host = !vmask::is_device_pointer(r), m_host = !vmask::is_device_pointer(mask);
-    if (r_host) dr = pool.get<double>(V);
-    if (m_host) dm = pool.get<uint8_t>(V);
-    ax.alloc(pool, n);
-    L.alloc(pool, n, spans, true);
-    if (pool.oom) { vmask::set_error("out of device memory (bias fit)"); return VRG_E_MEM; }
-    if (r_host) VB_TRY(hipMemcpy((void*)dr, r, V * 8, hipMemcpyHostToDevice));
-    if (m_host) VB_TRY(hipMemcpy((void*)dm, mask, V, hipMemcpyHostToDevice));
+    double* own_r = nullptr; uint8_t* own_m = nullptr;
+    if ((r_host && mem.grab(&own_r, V, "residual")) || (m_host && mem.grab(&own_m, V, "mask")) || ax.alloc(mem, n) || L.alloc(mem, n, spans, true)) {
+        vmask::set_error("out of device memory (bias fit)");
+        return VRG_E_MEM;
+    }
+    const double* dr = r_host ? own_r : r; const uint8_t* dm = m_host ? own_m : mask;
+    if (r_host) VMASK_TRY(hipMemcpy(own_r, r, V * 8, hipMemcpyHostToDevice));
+    if (m_host) VMASK_TRY(hipMemcpy(own_m, mask, V, hipMemcpyHostToDevice));
     const int src = ax.set(n, spans);
     if (src) return src;
     launch_fit(dr, dm, n, ax, L);
-    VB_TRY(hipGetLastError());
-    VB_TRY(hipDeviceSynchronize());
-    VB_TRY(hipMemcpy(phi, L.phi, (size_t)ax.dev[0].K * ax.dev[1].K * ax.dev[2].K * 8, hipMemcpyDefault));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipMemcpy(phi, L.phi, (size_t)ax.dev[0].K * ax.dev[1].K * ax.dev[2].K * 8, hipMemcpyDefault));
     return VRG_OK;
 }
 
@@ -541,22 +527,23 @@ extern "C" int vmask_bias_eval(int device, const double* phi, const int* spans, 
     if (rc) return rc;
     const int64_t n[3] = {n0, n1, n2};
     const size_t V = (size_t)n0 * n1 * n2;
-    Pool pool;
+    DevMem mem;
     AxisSet ax;
     Lattice L;
-    double* dout = out;
     const bool out_host = !vmask::is_device_pointer(out);
-    if (out_host) dout = pool.get<double>(V);
-    ax.alloc(pool, n);
-    L.alloc(pool, n, spans, false);
-    if (pool.oom) { vmask::set_error("out of device memory (bias evaluation)"); return VRG_E_MEM; }
+    double* own_out = nullptr;
+    if ((out_host && mem.grab(&own_out, V, "output")) || ax.alloc(mem, n) || L.alloc(mem, n, spans, false)) {
+        vmask::set_error("out of device memory (bias evaluation)");
+        return VRG_E_MEM;
+    }
+    double* dout = out_host ? own_out : out;
     const int src = ax.set(n, spans);
     if (src) return src;
-    VB_TRY(hipMemcpy(L.phi, phi, (size_t)ax.dev[0].K * ax.dev[1].K * ax.dev[2].K * 8, hipMemcpyDefault));
+    VMASK_TRY(hipMemcpy(L.phi, phi, (size_t)ax.dev[0].K * ax.dev[1].K * ax.dev[2].K * 8, hipMemcpyDefault));
     launch_eval(n, ax, L, dout, false);
-    VB_TRY(hipGetLastError());
-    VB_TRY(hipDeviceSynchronize());
-    if (out_host) VB_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    if (out_host) VMASK_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 
@@ -570,25 +557,25 @@ extern "C" int vmask_bias_log_field(int device, const double* v, const uint8_t* 
     if (rc) return rc;
     const int64_t n[3] = {n0, n1, n2};
     const size_t V = (size_t)n0 * n1 * n2;
-    Pool pool;
-    const double* dv = v; const uint8_t* dm = mask; double* db = b;
+    DevMem mem;
     const bool v_host = !vmask::is_device_pointer(v), m_host = !vmask::is_device_pointer(mask), b_host = !vmask::is_device_pointer(b);
-    if (v_host) dv = pool.get<double>(V);
-    if (m_host) dm = pool.get<uint8_t>(V);
-    if (b_host) db = pool.get<double>(V);
-    double* r = pool.get<double>(V);
-    unsigned long long* total = pool.get<unsigned long long>(1);
-    if (pool.oom) { vmask::set_error("out of device memory (bias field: the log volume, the mask, the field and the residual; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    if (v_host) VB_TRY(hipMemcpy((void*)dv, v, V * 8, hipMemcpyHostToDevice));
-    if (m_host) VB_TRY(hipMemcpy((void*)dm, mask, V, hipMemcpyHostToDevice));
-    VB_TRY(hipMemset(total, 0, sizeof(unsigned long long)));
+    double* own_v = nullptr; uint8_t* own_m = nullptr; double* own_b = nullptr; double* r = nullptr; unsigned long long* total = nullptr;
+    if ((v_host && mem.grab(&own_v, V, "log volume")) || (m_host && mem.grab(&own_m, V, "mask")) || (b_host && mem.grab(&own_b, V, "log field")) ||
+        mem.grab(&r, V, "residual") || mem.grab(&total, 1, "counter")) {
+        vmask::set_error("out of device memory (bias field: the log volume, the mask, the field and the residual; volumes are not processed in slabs)");
+        return VRG_E_MEM;
+    }
+    const double* dv = v_host ? own_v : v; const uint8_t* dm = m_host ? own_m : mask; double* db = b_host ? own_b : b;
+    if (v_host) VMASK_TRY(hipMemcpy(own_v, v, V * 8, hipMemcpyHostToDevice));
+    if (m_host) VMASK_TRY(hipMemcpy(own_m, mask, V, hipMemcpyHostToDevice));
+    VMASK_TRY(hipMemset(total, 0, sizeof(unsigned long long)));
     k_bias_count<<<stream_grid((int64_t)V), BT>>>(dm, (int64_t)V, total);
     unsigned long long inside = 0;
-    VB_TRY(hipMemcpy(&inside, total, sizeof inside, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&inside, total, sizeof inside, hipMemcpyDeviceToHost));
     if (!inside) { vmask::set_error("bias: the mask is empty"); return VRG_E_ARG; }
-    rc = run_loop(dv, dm, n, a, db, r, pool, trace, ntrace);
+    rc = run_loop(dv, dm, n, a, db, r, mem, trace, ntrace);
     if (rc) return rc;
-    if (b_host) VB_TRY(hipMemcpy(b, db, V * 8, hipMemcpyDeviceToHost));
+    if (b_host) VMASK_TRY(hipMemcpy(b, db, V * 8, hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 

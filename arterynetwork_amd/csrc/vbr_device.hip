@@ -37,6 +37,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 #include "vseg_slots.h"
 
 namespace {
@@ -260,19 +261,6 @@ __global__ void __launch_bounds__(TPB) k_br_emit(const int64_t* __restrict__ off
     }
 }
 
-struct Work {
-    std::vector<void*> owned;
-    ~Work() { for (void* p : owned) (void)hipFree(p); }
-    // *p (re)allocated for count elements; what it held before is freed
-    template <class T> int grab(T** p, size_t count, const char* what) {
-        if (*p) { owned.erase(std::find(owned.begin(), owned.end(), (void*)*p)); (void)hipFree(*p); *p = nullptr; }
-        const int rc = dev_alloc(p, count, what);
-        if (!rc) owned.push_back(*p);
-        return rc;
-    }
-};
-#define BR_GRAB(p, count, what) do { int rc_ = w.grab(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
 struct Graph {                                                          // one build: what the kernels after it need
     uint32_t n = 0, nseg = 0; u64 total = 0; int label_rounds = 0;
     u64 nodes = 0, clusters = 0, endpts = 0, pass = 0, branches = 0, entries = 0, iso = 0, dropped = 0;
@@ -287,38 +275,38 @@ struct Buffers {
 };
 
 // the graph of the 0/1 volume vol (device); pr.on: run the spur test as well
-int build_graph(int device, Work& w, Buffers& b, const uint8_t* vol, Dim d, const Prune& pr, Graph& g) {
+int build_graph(int device, DevMem& mem, Buffers& b, const uint8_t* vol, Dim d, const Prune& pr, Graph& g) {
     const u64 V = (u64)d.n0 * d.n1 * d.n2;
     g = Graph();
-    SG_TRY(hipMemsetAsync(b.ctr, 0, (size_t)C_N * C_PITCH * sizeof(u64), 0));
+    VMASK_TRY(hipMemsetAsync(b.ctr, 0, (size_t)C_N * C_PITCH * sizeof(u64), 0));
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(vol) & 15u);
     const uint4* base = reinterpret_cast<const uint4*>(vol - lead);
     const u64 nwords = (lead + V + 15u) / 16u;
     const int gvol = grid_for(nwords, GRID_VOLUME);
     k_seg_count<<<gvol, TPB>>>(base, nwords, lead, V, b.ctr + c_at(C_OBJ));
     u64 nobj = 0;
-    SG_TRY(hipMemcpy(&nobj, b.ctr + c_at(C_OBJ), sizeof(u64), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&nobj, b.ctr + c_at(C_OBJ), sizeof(u64), hipMemcpyDeviceToHost));
     if (nobj >= (1ull << 30)) { vmask::set_error("more than 2^30 object voxels"); return VRG_E_ARG; }
     const uint32_t n = g.n = (uint32_t)nobj;
     if (!n) return VRG_OK;
     if (n > b.cap_n) {                                                  // (the first build: pruning only removes voxels)
         b.bits = hash_bits(n);
-        BR_GRAB(b.tab, (size_t)1 << b.bits, "index table");
-        BR_GRAB(b.list, n, "voxel list"); BR_GRAB(b.word, n, "neighbourhoods"); BR_GRAB(b.jmask, n, "junction neighbours");
-        BR_GRAB(b.P, n, "cluster labels"); BR_GRAB(b.rep, n, "representatives"); BR_GRAB(b.members, n, "member counts");
-        BR_GRAB(b.ends, n, "branch ends"); BR_GRAB(b.best, n, "spur choice"); BR_GRAB(b.nodeid, n, "node ids");
+        VMASK_GRAB(b.tab, (size_t)1 << b.bits, "index table");
+        VMASK_GRAB(b.list, n, "voxel list"); VMASK_GRAB(b.word, n, "neighbourhoods"); VMASK_GRAB(b.jmask, n, "junction neighbours");
+        VMASK_GRAB(b.P, n, "cluster labels"); VMASK_GRAB(b.rep, n, "representatives"); VMASK_GRAB(b.members, n, "member counts");
+        VMASK_GRAB(b.ends, n, "branch ends"); VMASK_GRAB(b.best, n, "spur choice"); VMASK_GRAB(b.nodeid, n, "node ids");
         b.cap_n = n;
     }
     // the segments: the capacities of a curve skeleton first, the stated ones where that is too little
     int64_t sc[5] = {0, 0, 0, 0, 0};
     if (!b.cap_seg) {
         b.cap_seg = (size_t)n + 16; b.cap_vox = 2 * (size_t)n + 16;
-        BR_GRAB(b.soff, b.cap_seg + 1, "segment offsets"); BR_GRAB(b.svox, b.cap_vox, "segment voxels");
+        VMASK_GRAB(b.soff, b.cap_seg + 1, "segment offsets"); VMASK_GRAB(b.svox, b.cap_vox, "segment voxels");
     }
     int rc = vmask_segments(device, vol, d.n0, d.n1, d.n2, sc, b.soff, (int64_t)b.cap_seg, b.svox, (int64_t)b.cap_vox);
     if (rc == VRG_E_ARG && ((u64)sc[0] > b.cap_seg || (u64)sc[1] > b.cap_vox)) {
         b.cap_seg = std::max<size_t>(b.cap_seg, (size_t)sc[0]); b.cap_vox = std::max<size_t>(b.cap_vox, (size_t)sc[1]);
-        BR_GRAB(b.soff, b.cap_seg + 1, "segment offsets"); BR_GRAB(b.svox, b.cap_vox, "segment voxels");
+        VMASK_GRAB(b.soff, b.cap_seg + 1, "segment offsets"); VMASK_GRAB(b.svox, b.cap_vox, "segment voxels");
         rc = vmask_segments(device, vol, d.n0, d.n1, d.n2, sc, b.soff, (int64_t)b.cap_seg, b.svox, (int64_t)b.cap_vox);
     }
     if (rc) return rc;
@@ -326,16 +314,16 @@ int build_graph(int device, Work& w, Buffers& b, const uint8_t* vol, Dim d, cons
     const uint32_t nseg = g.nseg = (uint32_t)sc[0];
     g.total = (u64)sc[1];
     if (nseg > b.cap_k) {
-        BR_GRAB(b.elen, nseg, "branch lengths"); BR_GRAB(b.sflag, nseg, "branch flags"); BR_GRAB(b.ska, nseg, "branch ends");
-        BR_GRAB(b.skb, nseg, "branch ends"); BR_GRAB(b.scl, nseg, "spur clusters");
+        VMASK_GRAB(b.elen, nseg, "branch lengths"); VMASK_GRAB(b.sflag, nseg, "branch flags"); VMASK_GRAB(b.ska, nseg, "branch ends");
+        VMASK_GRAB(b.skb, nseg, "branch ends"); VMASK_GRAB(b.scl, nseg, "spur clusters");
         b.cap_k = nseg;
     }
     Hash h{b.tab, (uint32_t)((1ull << b.bits) - 1ull), 32u - (uint32_t)b.bits};
-    SG_TRY(hipMemsetAsync(b.tab, 0xff, ((size_t)1 << b.bits) * sizeof(u64), 0));
-    SG_TRY(hipMemsetAsync(b.rep, 0, (size_t)n * sizeof(u64), 0));
-    SG_TRY(hipMemsetAsync(b.members, 0, (size_t)n * sizeof(uint32_t), 0));
-    SG_TRY(hipMemsetAsync(b.ends, 0, (size_t)n * sizeof(uint32_t), 0));
-    SG_TRY(hipMemsetAsync(b.best, 0xff, (size_t)n * sizeof(u64), 0));
+    VMASK_TRY(hipMemsetAsync(b.tab, 0xff, ((size_t)1 << b.bits) * sizeof(u64), 0));
+    VMASK_TRY(hipMemsetAsync(b.rep, 0, (size_t)n * sizeof(u64), 0));
+    VMASK_TRY(hipMemsetAsync(b.members, 0, (size_t)n * sizeof(uint32_t), 0));
+    VMASK_TRY(hipMemsetAsync(b.ends, 0, (size_t)n * sizeof(uint32_t), 0));
+    VMASK_TRY(hipMemsetAsync(b.best, 0xff, (size_t)n * sizeof(u64), 0));
     const int gslot = grid_for(n, GRID_LIST);
     k_seg_compact<<<gvol, TPB>>>(base, nwords, lead, V, n, b.list, h, b.ctr + c_at(C_CURSOR));
     k_br_gather<<<gslot, TPB>>>(vol, d, b.list, n, b.word, b.P, b.ctr);
@@ -345,7 +333,7 @@ int build_graph(int device, Work& w, Buffers& b, const uint8_t* vol, Dim d, cons
         u64* c = b.ctr + c_at(C_LABEL + g.label_rounds);
         k_br_hook<<<gslot, TPB>>>(b.list, b.jmask, n, d, h, b.P, c);
         u64 lowered = 0;
-        SG_TRY(hipMemcpy(&lowered, c, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&lowered, c, sizeof(u64), hipMemcpyDeviceToHost));
         g.label_rounds++;
         if (!lowered) break;
     }
@@ -356,54 +344,40 @@ int build_graph(int device, Work& w, Buffers& b, const uint8_t* vol, Dim d, cons
     return VRG_OK;
 }
 
-// a caller's array that the kernels write: itself when it lives on the device, a device copy otherwise
-template <class T> struct Out {
-    T* user = nullptr; T* dev = nullptr; size_t count = 0;
-    int open(Work& w, T* p, size_t n, const char* what) {
-        user = p; count = n;
-        if (vmask::is_device_pointer(p)) { dev = p; return VRG_OK; }
-        return w.grab(&dev, n, what);
-    }
-    int close() {
-        if (dev != user && count) SG_TRY(hipMemcpy(user, dev, count * sizeof(T), hipMemcpyDeviceToHost));
-        return VRG_OK;
-    }
-};
-
 int branches(int device, const uint8_t* volume, Dim d, int64_t min_len, double factor, const double* dist, int64_t max_rounds,
              uint8_t* skeleton, int64_t* counts, int64_t* nodes, int64_t cap_node, int64_t* ends, int64_t* offsets, int64_t cap_branch,
              int64_t* voxels, int64_t cap_vox) {
     const u64 V = (u64)d.n0 * d.n1 * d.n2;
     const bool want = nodes != nullptr;
-    Work w;
+    DevMem mem;
     Buffers b;
     uint8_t* vol = nullptr;
-    BR_GRAB(vol, V, "volume");
+    VMASK_GRAB(vol, V, "volume");
     const int gbyte = grid_for(V, 4 * GRID_VOLUME);
     if (vmask::is_device_pointer(volume)) k_br_binary<<<gbyte, TPB>>>(volume, vol, V);
     else {
-        SG_TRY(hipMemcpy(vol, volume, V, hipMemcpyHostToDevice));
+        VMASK_TRY(hipMemcpy(vol, volume, V, hipMemcpyHostToDevice));
         k_br_binary<<<gbyte, TPB>>>(vol, vol, V);
     }
     Prune pr{min_len, factor, dist, V, 0};
     if (dist && !vmask::is_device_pointer(dist)) {
         double* dd = nullptr;
-        BR_GRAB(dd, V, "distance volume");
-        SG_TRY(hipMemcpy(dd, dist, V * sizeof(double), hipMemcpyHostToDevice));
+        VMASK_GRAB(dd, V, "distance volume");
+        VMASK_TRY(hipMemcpy(dd, dist, V * sizeof(double), hipMemcpyHostToDevice));
         pr.dist = dd;
     }
-    BR_GRAB(b.ctr, (size_t)C_N * C_PITCH, "counters");
+    VMASK_GRAB(b.ctr, (size_t)C_N * C_PITCH, "counters");
     Graph g;
     int64_t rounds = 0;
     u64 spurs = 0, removed = 0;
     for (;;) {
         pr.on = rounds < max_rounds && (min_len > 0 || (dist && factor > 0.0));
-        int rc = build_graph(device, w, b, vol, d, pr, g);
+        int rc = build_graph(device, mem, b, vol, d, pr, g);
         if (rc) return rc;
         if (!pr.on || !g.nseg) break;
         k_br_clear<<<grid_for(g.total, GRID_LIST), TPB>>>(b.soff, b.svox, g.nseg, g.total, V, b.scl, b.best, g.n, vol, b.ctr);
         u64 hc[C_PITCH + 1];
-        SG_TRY(hipMemcpy(hc, b.ctr + c_at(C_SPURS), sizeof(hc), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hc, b.ctr + c_at(C_SPURS), sizeof(hc), hipMemcpyDeviceToHost));
         if (!hc[0]) break;                                              // the graph just built is the final one
         rounds++; spurs += hc[0]; removed += hc[C_PITCH];
         rc = vmask_skeleton(device, vol, d.n0, d.n1, d.n2, vol, nullptr, nullptr);     // (reads all of its input before it writes)
@@ -413,10 +387,10 @@ int branches(int device, const uint8_t* volume, Dim d, int64_t min_len, double f
     uint4* rec = nullptr;
     const u64 cap_rec = want ? std::min<u64>((u64)cap_node, g.n) : 0;
     if (g.n) {
-        if (cap_rec) BR_GRAB(rec, cap_rec, "node records");
+        if (cap_rec) VMASK_GRAB(rec, cap_rec, "node records");
         k_br_nodes<<<grid_for(g.n, GRID_LIST), TPB>>>(b.list, b.word, g.n, b.P, b.rep, b.members, b.ends, rec, cap_rec, b.ctr);
         u64 hc[(C_DROPPED - C_ISO) * C_PITCH + 1];
-        SG_TRY(hipMemcpy(hc, b.ctr + c_at(C_ISO), sizeof(hc), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hc, b.ctr + c_at(C_ISO), sizeof(hc), hipMemcpyDeviceToHost));
         g.iso = hc[0]; g.nodes = hc[c_at(C_NODES - C_ISO)]; g.clusters = hc[c_at(C_CLUSTERS - C_ISO)]; g.endpts = hc[c_at(C_ENDPTS - C_ISO)];
         g.pass = hc[c_at(C_PASS - C_ISO)]; g.branches = hc[c_at(C_BRANCH - C_ISO)]; g.entries = hc[c_at(C_ENTRIES - C_ISO)];
         g.dropped = hc[c_at(C_DROPPED - C_ISO)];
@@ -434,7 +408,7 @@ int branches(int device, const uint8_t* volume, Dim d, int64_t min_len, double f
         if (!g.branches) { rc = put(offsets, &zero, 1); if (rc) return rc; }
         if (g.nodes) try {                                              // the records alone go to the host: sorted by representative there
             std::vector<uint4> hrec(g.nodes);
-            SG_TRY(hipMemcpy(hrec.data(), rec, g.nodes * sizeof(uint4), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(hrec.data(), rec, g.nodes * sizeof(uint4), hipMemcpyDeviceToHost));
             std::sort(hrec.begin(), hrec.end(), [](const uint4& x, const uint4& y) { return x.x < y.x; });
             std::vector<int64_t> table(4 * g.nodes);
             std::vector<uint32_t> slots(g.nodes);
@@ -445,38 +419,38 @@ int branches(int device, const uint8_t* volume, Dim d, int64_t min_len, double f
             rc = put(nodes, table.data(), table.size());
             if (rc) return rc;
             uint32_t* dslots = nullptr;
-            BR_GRAB(dslots, g.nodes, "node slots");
-            SG_TRY(hipMemcpy(dslots, slots.data(), g.nodes * sizeof(uint32_t), hipMemcpyHostToDevice));
+            VMASK_GRAB(dslots, g.nodes, "node slots");
+            VMASK_TRY(hipMemcpy(dslots, slots.data(), g.nodes * sizeof(uint32_t), hipMemcpyHostToDevice));
             k_br_nodeid<<<grid_for(g.nodes, GRID_LIST), TPB>>>(dslots, (uint32_t)g.nodes, g.n, b.nodeid);
         } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (node records)"); return VRG_E_MEM; }
         if (g.branches) {
             u64* bidx = nullptr; u64* voff = nullptr; void* tmp = nullptr;
-            BR_GRAB(bidx, g.nseg, "branch indices"); BR_GRAB(voff, g.nseg, "branch offsets");
+            VMASK_GRAB(bidx, g.nseg, "branch indices"); VMASK_GRAB(voff, g.nseg, "branch offsets");
             auto kept = rocprim::make_transform_iterator(b.elen, Positive());
             auto lens = rocprim::make_transform_iterator(b.elen, Widen());
             size_t tb = 0, tb2 = 0;
-            SG_TRY(rocprim::exclusive_scan(nullptr, tb, kept, bidx, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
-            SG_TRY(rocprim::exclusive_scan(nullptr, tb2, lens, voff, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
+            VMASK_TRY(rocprim::exclusive_scan(nullptr, tb, kept, bidx, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
+            VMASK_TRY(rocprim::exclusive_scan(nullptr, tb2, lens, voff, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
             tb = std::max(tb, tb2);
             uint8_t* tmpb = nullptr;
-            BR_GRAB(tmpb, tb, "scan space");
+            VMASK_GRAB(tmpb, tb, "scan space");
             tmp = tmpb;
-            SG_TRY(rocprim::exclusive_scan(tmp, tb, kept, bidx, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
-            SG_TRY(rocprim::exclusive_scan(tmp, tb, lens, voff, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
+            VMASK_TRY(rocprim::exclusive_scan(tmp, tb, kept, bidx, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
+            VMASK_TRY(rocprim::exclusive_scan(tmp, tb, lens, voff, 0ull, (size_t)g.nseg, rocprim::plus<u64>()));
             Out<int64_t> oe, oo, ov;
-            if ((rc = oe.open(w, ends, 2 * g.branches, "branch ends")) || (rc = oo.open(w, offsets, g.branches + 1, "offsets")) ||
-                (rc = ov.open(w, voxels, g.entries, "branch voxels"))) return rc;
+            if ((rc = oe.open(mem, ends, 2 * g.branches, "branch ends")) || (rc = oo.open(mem, offsets, g.branches + 1, "offsets")) ||
+                (rc = ov.open(mem, voxels, g.entries, "branch voxels"))) return rc;
             k_br_emit<<<grid_for(g.total, GRID_LIST), TPB>>>(b.soff, b.svox, g.nseg, g.total, b.list, b.word, b.rep, b.elen, b.sflag, b.ska, b.skb,
                                                             bidx, voff, b.nodeid, g.branches, g.entries, oe.dev, oo.dev, ov.dev);
             const int64_t last = (int64_t)g.entries;
-            SG_TRY(hipMemcpy(oo.dev + g.branches, &last, sizeof(int64_t), hipMemcpyHostToDevice));
-            SG_TRY(hipGetLastError());
+            VMASK_TRY(hipMemcpy(oo.dev + g.branches, &last, sizeof(int64_t), hipMemcpyHostToDevice));
+            VMASK_TRY(hipGetLastError());
             if ((rc = oe.close()) || (rc = oo.close()) || (rc = ov.close())) return rc;
         }
     }
-    if (skeleton) SG_TRY(hipMemcpy(skeleton, vol, V, vmask::is_device_pointer(skeleton) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    SG_TRY(hipGetLastError());
-    SG_TRY(hipDeviceSynchronize());
+    if (skeleton) VMASK_TRY(hipMemcpy(skeleton, vol, V, vmask::is_device_pointer(skeleton) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
     return VRG_OK;
 }
 

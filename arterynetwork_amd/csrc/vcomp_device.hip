@@ -34,6 +34,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 #include "vseg_slots.h"
 
 namespace {
@@ -294,49 +295,6 @@ __global__ void __launch_bounds__(TPB) k_comp_finish(Table t, u64 K, const uint8
     flush(h, K, cc);
 }
 
-struct Work {
-    std::vector<void*> owned;
-    ~Work() { for (void* p : owned) (void)hipFree(p); }
-    template <class T> int grab(T** p, size_t count, const char* what) {
-        const int rc = dev_alloc(p, count, what);
-        if (!rc) owned.push_back(*p);
-        return rc;
-    }
-};
-#define COMP_GRAB(p, count, what) do { int rc_ = w.grab(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-// a caller's array that the kernels read: itself when it lives on the device, a device copy otherwise
-template <class T> int bring(Work& w, const T* p, size_t n, const char* what, const T** dev) {
-    if (!n || vmask::is_device_pointer(p)) { *dev = p; return VRG_OK; }
-    T* d = nullptr;
-    const int rc = w.grab(&d, n, what);
-    if (rc) return rc;
-    SG_TRY(hipMemcpy(d, p, n * sizeof(T), hipMemcpyHostToDevice));
-    *dev = d;
-    return VRG_OK;
-}
-// a caller's array that the kernels write: itself when it lives on the device, a device copy otherwise
-template <class T> struct Out {
-    T* user = nullptr; T* dev = nullptr; size_t count = 0;
-    int open(Work& w, T* p, size_t n, const char* what) {
-        user = p; count = n;
-        if (vmask::is_device_pointer(p)) { dev = p; return VRG_OK; }
-        return w.grab(&dev, n, what);
-    }
-    int close() {
-        if (dev != user && count) SG_TRY(hipMemcpy(user, dev, count * sizeof(T), hipMemcpyDeviceToHost));
-        return VRG_OK;
-    }
-};
-
-// a caller's small array on the host
-int fetch(const int64_t* p, size_t n, std::vector<int64_t>& out) {
-    out.resize(n);
-    if (!n) return VRG_OK;
-    if (vmask::is_device_pointer(p)) SG_TRY(hipMemcpy(out.data(), p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    else std::copy(p, p + n, out.begin());
-    return VRG_OK;
-}
 bool ascends_from_zero(const std::vector<int64_t>& off) {
     if (off.empty() || off[0] != 0) return false;
     for (size_t k = 1; k < off.size(); k++)
@@ -358,14 +316,14 @@ struct Args {
 
 int compartments(const Args& g, u64 V) {
     const u64 B = (u64)g.B, N = (u64)g.N, K = (u64)g.K;
-    Work w;
+    DevMem mem;
     int rc;
     int64_t total = 0;
     if (B) {
         int64_t edge[2] = {0, 0};
         if (vmask::is_device_pointer(g.offsets)) {
-            SG_TRY(hipMemcpy(&edge[0], g.offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
-            SG_TRY(hipMemcpy(&edge[1], g.offsets + B, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&edge[0], g.offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&edge[1], g.offsets + B, sizeof(int64_t), hipMemcpyDeviceToHost));
         } else { edge[0] = g.offsets[0]; edge[1] = g.offsets[B]; }
         if (edge[0] != 0 || edge[1] < 2 * (int64_t)B || edge[1] > ((int64_t)1 << 40)) { vmask::set_error("offsets do not describe branches of at least two entries"); return VRG_E_ARG; }
         total = edge[1];
@@ -383,29 +341,29 @@ int compartments(const Args& g, u64 V) {
     } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (compartment lists)"); return VRG_E_MEM; }
     const u64 ni = ivox.size(), nb = bvox.size(), M = all.size();
     Table t{nullptr, nullptr, nullptr, nullptr, B, N};
-    if ((rc = bring(w, g.offsets, B ? B + 1 : 0, "offsets", &t.off)) || (rc = bring(w, g.voxels, (size_t)total, "branch voxels", &t.vox)) ||
-        (rc = bring(w, g.ends, 2 * B, "branch ends", &t.ends)) || (rc = bring(w, g.nodevox, N, "node voxels", &t.nodevox))) return rc;
+    if ((rc = bring(mem, g.offsets, B ? B + 1 : 0, "offsets", &t.off)) || (rc = bring(mem, g.voxels, (size_t)total, "branch voxels", &t.vox)) ||
+        (rc = bring(mem, g.ends, 2 * B, "branch ends", &t.ends)) || (rc = bring(mem, g.nodevox, N, "node voxels", &t.nodevox))) return rc;
     int64_t* lists = nullptr;
     uint8_t* hit = nullptr;
     u64* ctr = nullptr;
     const size_t words = 2 * (K + 1) + ni + nb + M;
-    COMP_GRAB(lists, words, "compartment lists"); COMP_GRAB(hit, M, "list marks"); COMP_GRAB(ctr, 2 * C_PITCH, "counters");
+    VMASK_GRAB(lists, words, "compartment lists"); VMASK_GRAB(hit, M, "list marks"); VMASK_GRAB(ctr, 2 * C_PITCH, "counters");
     try {
         std::vector<int64_t> pack;
         pack.reserve(words);
         for (const std::vector<int64_t>* v : {&ioff, &boff, &ivox, &bvox, &all}) pack.insert(pack.end(), v->begin(), v->end());
-        SG_TRY(hipMemcpy(lists, pack.data(), words * sizeof(int64_t), hipMemcpyHostToDevice));
+        VMASK_TRY(hipMemcpy(lists, pack.data(), words * sizeof(int64_t), hipMemcpyHostToDevice));
     } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (compartment lists)"); return VRG_E_MEM; }
     const Lists L{lists, lists + 2 * (K + 1), lists + (K + 1), lists + 2 * (K + 1) + ni};
     const int64_t* dall = lists + 2 * (K + 1) + ni + nb;
-    SG_TRY(hipMemsetAsync(ctr, 0, 2 * C_PITCH * sizeof(u64), 0));
-    if (M) SG_TRY(hipMemsetAsync(hit, 0, M, 0));
+    VMASK_TRY(hipMemsetAsync(ctr, 0, 2 * C_PITCH * sizeof(u64), 0));
+    if (M) VMASK_TRY(hipMemsetAsync(hit, 0, M, 0));
     const u64 most = std::max(std::max(B, (u64)total), std::max(N, std::max(ni, nb)));
     u64 bad = 0;
     if (most) {
         k_comp_check<<<grid_for(most, GRID_LIST), TPB>>>(t, (u64)total, V, L, K, ni, nb, dall, M, hit, ctr);
         if (M) k_comp_unhit<<<grid_for(M, GRID_LIST), TPB>>>(hit, M, ctr);
-        SG_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
     }
     if (bad) {
         vmask::set_error("the branch table or the compartment lists do not fit: offsets, voxels, ends, node voxels or end entries out of range, "
@@ -415,22 +373,22 @@ int compartments(const Args& g, u64 V) {
 
     Out<uint8_t> oec, onc, obc;
     Out<int64_t> oed, oel, ond, onl, obl;
-    if ((rc = oec.open(w, g.entry_comp, (size_t)total, "entry compartments")) || (rc = oed.open(w, g.entry_depth, (size_t)total, "entry depths")) ||
-        (rc = oel.open(w, g.entry_level, (size_t)total, "entry levels")) || (rc = onc.open(w, g.node_comp, N, "node compartments")) ||
-        (rc = ond.open(w, g.node_depth, N, "node depths")) || (rc = onl.open(w, g.node_level, N, "node levels")) ||
-        (rc = obc.open(w, g.branch_comp, B, "branch compartments")) || (rc = obl.open(w, g.branch_level, B, "branch levels"))) return rc;
+    if ((rc = oec.open(mem, g.entry_comp, (size_t)total, "entry compartments")) || (rc = oed.open(mem, g.entry_depth, (size_t)total, "entry depths")) ||
+        (rc = oel.open(mem, g.entry_level, (size_t)total, "entry levels")) || (rc = onc.open(mem, g.node_comp, N, "node compartments")) ||
+        (rc = ond.open(mem, g.node_depth, N, "node depths")) || (rc = onl.open(mem, g.node_level, N, "node levels")) ||
+        (rc = obc.open(mem, g.branch_comp, B, "branch compartments")) || (rc = obl.open(mem, g.branch_level, B, "branch levels"))) return rc;
     Nodes nd{nullptr, nullptr, nullptr};
     Pairs pr{nullptr, nullptr, nullptr};
     uint8_t* twice = nullptr;
     u64* cc = nullptr;
-    COMP_GRAB(nd.f, K * N, "node flags"); COMP_GRAB(nd.d, K * N, "node depths per compartment"); COMP_GRAB(nd.l, K * N, "node levels per compartment");
-    COMP_GRAB(pr.f, K * B, "pair flags"); COMP_GRAB(pr.a, K * B, "pair hops"); COMP_GRAB(pr.b, K * B, "pair hops");
-    COMP_GRAB(twice, (size_t)total, "entry marks"); COMP_GRAB(cc, CC_N * (K + 1), "compartment counts");
-    SG_TRY(hipMemsetAsync(cc, 0, CC_N * (K + 1) * sizeof(u64), 0));
+    VMASK_GRAB(nd.f, K * N, "node flags"); VMASK_GRAB(nd.d, K * N, "node depths per compartment"); VMASK_GRAB(nd.l, K * N, "node levels per compartment");
+    VMASK_GRAB(pr.f, K * B, "pair flags"); VMASK_GRAB(pr.a, K * B, "pair hops"); VMASK_GRAB(pr.b, K * B, "pair hops");
+    VMASK_GRAB(twice, (size_t)total, "entry marks"); VMASK_GRAB(cc, CC_N * (K + 1), "compartment counts");
+    VMASK_TRY(hipMemsetAsync(cc, 0, CC_N * (K + 1) * sizeof(u64), 0));
     if (total) {
-        SG_TRY(hipMemsetAsync(twice, 0, (size_t)total, 0));
-        SG_TRY(hipMemsetAsync(oed.dev, 0xff, (size_t)total * sizeof(int64_t), 0));                        // the keys: NONE64
-        SG_TRY(hipMemsetAsync(oel.dev, 0xff, (size_t)total * sizeof(int64_t), 0));
+        VMASK_TRY(hipMemsetAsync(twice, 0, (size_t)total, 0));
+        VMASK_TRY(hipMemsetAsync(oed.dev, 0xff, (size_t)total * sizeof(int64_t), 0));                        // the keys: NONE64
+        VMASK_TRY(hipMemsetAsync(oel.dev, 0xff, (size_t)total * sizeof(int64_t), 0));
     }
     const int gp = grid_for(K * B, GRID_LIST);
     int64_t rounds[2] = {0, 0};
@@ -440,10 +398,10 @@ int compartments(const Args& g, u64 V) {
     for (int phase = 0; phase < 2; phase++)
         for (u64 lowered = 1; B && N && lowered;) {
             if (rounds[phase] == limit) { vmask::set_error(phase ? "the levels did not settle within one round per node" : "the depths did not settle within one round per node"); return VRG_E_INTERNAL; }
-            SG_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
+            VMASK_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
             if (phase) k_comp_level<<<gp, TPB>>>(t, K, nd, pr, ctr);
             else k_comp_relax<<<gp, TPB>>>(t, K, nd, pr, ctr);
-            SG_TRY(hipMemcpy(&lowered, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&lowered, ctr, sizeof(u64), hipMemcpyDeviceToHost));
             rounds[phase]++;
         }
     if (B) {
@@ -452,17 +410,17 @@ int compartments(const Args& g, u64 V) {
     }
     if (N) k_comp_merge<<<grid_for(N, GRID_LIST), TPB>>>(N, K, nd, onc.dev, ond.dev, onl.dev, cc);
     if (B) k_comp_finish<<<grid_for(B, GRID_LIST), TPB>>>(t, K, onc.dev, ond.dev, onl.dev, twice, oec.dev, oed.dev, oel.dev, obc.dev, obl.dev, cc);
-    SG_TRY(hipGetLastError());
+    VMASK_TRY(hipGetLastError());
     if ((rc = oec.close()) || (rc = oed.close()) || (rc = oel.close()) || (rc = onc.close()) || (rc = ond.close()) || (rc = onl.close()) ||
         (rc = obc.close()) || (rc = obl.close())) return rc;
     try {
         std::vector<int64_t> hcc(CC_N * (K + 1));
-        SG_TRY(hipMemcpy(hcc.data(), cc, hcc.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hcc.data(), cc, hcc.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         if ((rc = put(g.comp_counts, hcc.data(), hcc.size()))) return rc;
     } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (compartment counts)"); return VRG_E_MEM; }
     if (g.counts && (rc = put(g.counts, rounds, 2))) return rc;
-    SG_TRY(hipGetLastError());
-    SG_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
     return VRG_OK;
 }
 

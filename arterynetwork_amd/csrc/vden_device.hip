@@ -26,6 +26,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 #pragma clang fp contract(off)
 
@@ -36,8 +37,6 @@ constexpr int DX = 64, DY = 16, DZ = 32;           // k_den_diffuse: the tile al
 constexpr int DR = DY / (DEN_T / DX);              // rows of a thread
 constexpr int DHALO = 2 * DX + 2 * DY;             // rim of a tile without the corners: the first 160 threads load one voxel each
 constexpr int MX = 64, MY = DEN_T / MX, MZ = 32;   // k_den_median
-
-#define VD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -215,31 +214,18 @@ __global__ void __launch_bounds__(DEN_T) k_den_median(const T* __restrict__ in, 
 }
 
 // ---------------------------------------------------------------- host
-struct Work {
-    void* p[4] = {};
-    int n = 0;
-    bool oom = false;
-    template <class T> T* get(size_t bytes) {
-        void* q = nullptr;
-        if (oom || n >= 4) { oom = true; return nullptr; }
-        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
-        p[n++] = q;
-        return (T*)q;
-    }
-    ~Work() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-
 template <class T>
 int diffuse(const T* volume, int64_t n0, int64_t n1, int64_t n2, const DiffGeo& g, int iterations, int function, double* out) {
     const size_t V = (size_t)n0 * n1 * n2;
-    Work w;
-    const T* din = volume; double* dout = out;
+    DevMem mem;
     const bool in_host = !vmask::is_device_pointer(volume), out_host = !vmask::is_device_pointer(out);
-    if (in_host) din = w.get<T>(V * sizeof(T));
-    if (out_host) dout = w.get<double>(V * 8);
-    double* work = w.get<double>(V * 8);
-    if (w.oom) { vmask::set_error("out of device memory (diffusion: the input, the output and one float64 volume; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    if (in_host) VD_TRY(hipMemcpy((void*)din, volume, V * sizeof(T), hipMemcpyHostToDevice));
+    T* own_in = nullptr; double* own_out = nullptr; double* work = nullptr;
+    if ((in_host && mem.grab(&own_in, V, "input")) || (out_host && mem.grab(&own_out, V, "output")) || mem.grab(&work, V, "work volume")) {
+        vmask::set_error("out of device memory (diffusion: the input, the output and one float64 volume; volumes are not processed in slabs)");
+        return VRG_E_MEM;
+    }
+    const T* din = in_host ? own_in : volume; double* dout = out_host ? own_out : out;
+    if (in_host) VMASK_TRY(hipMemcpy(own_in, volume, V * sizeof(T), hipMemcpyHostToDevice));
     const dim3 grid((unsigned)((n2 + DX - 1) / DX), (unsigned)((n1 + DY - 1) / DY), (unsigned)((n0 + DZ - 1) / DZ));
     for (int i = 0; i < iterations; i++) {
         double* dst = (iterations - 1 - i) % 2 == 0 ? dout : work;     // the last step lands in out
@@ -252,9 +238,9 @@ int diffuse(const T* volume, int64_t n0, int64_t n1, int64_t n2, const DiffGeo& 
             else k_den_diffuse<double, 1><<<grid, DEN_T>>>(src, dst, g);
         }
     }
-    VD_TRY(hipGetLastError());
-    VD_TRY(hipDeviceSynchronize());
-    if (out_host) VD_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    if (out_host) VMASK_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 
@@ -267,13 +253,15 @@ void median_launch(const T* in, T* out, int64_t n0, int64_t n1, int64_t n2) {
 template <class T>
 int median(const T* volume, int64_t n0, int64_t n1, int64_t n2, int r0, int r1, int r2, T* out) {
     const size_t V = (size_t)n0 * n1 * n2;
-    Work w;
-    const T* din = volume; T* dout = out;
+    DevMem mem;
     const bool in_host = !vmask::is_device_pointer(volume), out_host = !vmask::is_device_pointer(out);
-    if (in_host) din = w.get<T>(V * sizeof(T));
-    if (out_host) dout = w.get<T>(V * sizeof(T));
-    if (w.oom) { vmask::set_error("out of device memory (median: the input and the output; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    if (in_host) VD_TRY(hipMemcpy((void*)din, volume, V * sizeof(T), hipMemcpyHostToDevice));
+    T* own_in = nullptr; T* own_out = nullptr;
+    if ((in_host && mem.grab(&own_in, V, "input")) || (out_host && mem.grab(&own_out, V, "output"))) {
+        vmask::set_error("out of device memory (median: the input and the output; volumes are not processed in slabs)");
+        return VRG_E_MEM;
+    }
+    const T* din = in_host ? own_in : volume; T* dout = out_host ? own_out : out;
+    if (in_host) VMASK_TRY(hipMemcpy(own_in, volume, V * sizeof(T), hipMemcpyHostToDevice));
     switch (r0 * 4 + r1 * 2 + r2) {
         case 0: median_launch<T, 0, 0, 0>(din, dout, n0, n1, n2); break;
         case 1: median_launch<T, 0, 0, 1>(din, dout, n0, n1, n2); break;
@@ -284,9 +272,9 @@ int median(const T* volume, int64_t n0, int64_t n1, int64_t n2, int r0, int r1, 
         case 6: median_launch<T, 1, 1, 0>(din, dout, n0, n1, n2); break;
         default: median_launch<T, 1, 1, 1>(din, dout, n0, n1, n2); break;
     }
-    VD_TRY(hipGetLastError());
-    VD_TRY(hipDeviceSynchronize());
-    if (out_host) VD_TRY(hipMemcpy(out, dout, V * sizeof(T), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    if (out_host) VMASK_TRY(hipMemcpy(out, dout, V * sizeof(T), hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 #include "vseg_slots.h"
 
 #pragma clang fp contract(off)
@@ -211,58 +212,6 @@ __global__ void __launch_bounds__(TPB) k_flow(Graph G, Scen sc, Space ws, Res ou
     }
 }
 
-struct Work {
-    std::vector<void*> owned;
-    ~Work() { for (void* p : owned) (void)hipFree(p); }
-    template <class T> int grab(T** p, size_t count, const char* what) {
-        const int rc = dev_alloc(p, count, what);
-        if (!rc) owned.push_back(*p);
-        return rc;
-    }
-};
-#define FLOW_GRAB(p, count, what) do { int rc_ = w.grab(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-// a caller's array that the kernels read: itself when it lives on the device, a device copy otherwise
-template <class T> int bring(Work& w, const T* p, size_t n, const char* what, const T** dev) {
-    if (!n || vmask::is_device_pointer(p)) { *dev = p; return VRG_OK; }
-    T* d = nullptr;
-    const int rc = w.grab(&d, n, what);
-    if (rc) return rc;
-    SG_TRY(hipMemcpy(d, p, n * sizeof(T), hipMemcpyHostToDevice));
-    *dev = d;
-    return VRG_OK;
-}
-// a host array to a new device array
-template <class T> int send(Work& w, const std::vector<T>& v, const char* what, const T** dev) {
-    T* d = nullptr;
-    const int rc = w.grab(&d, v.size(), what);
-    if (rc) return rc;
-    if (!v.empty()) SG_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = d;
-    return VRG_OK;
-}
-// a caller's array that the kernels write: itself when it lives on the device, a device copy otherwise
-template <class T> struct Out {
-    T* user = nullptr; T* dev = nullptr; size_t count = 0;
-    int open(Work& w, T* p, size_t n, const char* what) {
-        user = p; count = n;
-        if (vmask::is_device_pointer(p)) { dev = p; return VRG_OK; }
-        return w.grab(&dev, n, what);
-    }
-    int close() {
-        if (dev != user && count) SG_TRY(hipMemcpy(user, dev, count * sizeof(T), hipMemcpyDeviceToHost));
-        return VRG_OK;
-    }
-};
-// a caller's small array on the host
-template <class T> int fetch(const T* p, size_t n, std::vector<T>& out) {
-    out.resize(n);
-    if (!n) return VRG_OK;
-    if (vmask::is_device_pointer(p)) SG_TRY(hipMemcpy(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost));
-    else std::copy(p, p + n, out.begin());
-    return VRG_OK;
-}
-
 struct Args {
     int64_t N, B; const int64_t* ends; const uint8_t* fixed; int64_t S; const double* R; int64_t rs; const double* pf; int64_t ps;
     double k, tol; int64_t max_iter; double* P; double* flow; int64_t* status; double* residual; int64_t* counts;
@@ -317,20 +266,20 @@ void derive(const int64_t* ends, const uint8_t* fixed, u64 N, u64 B, Topology& t
 
 int flow(const Args& a) {
     const u64 N = (u64)a.N, B = (u64)a.B, S = (u64)a.S;
-    Work w;
+    DevMem mem;
     int rc;
     const u64 nR = B * (a.rs ? S : 1), nP = N * (a.ps ? S : 1);
     const int64_t* ends = nullptr; const uint8_t* fixed = nullptr; const double* R = nullptr; const double* pf = nullptr;
-    if ((rc = bring(w, a.ends, 2 * B, "branch ends", &ends)) || (rc = bring(w, a.fixed, N, "fixed flags", &fixed)) ||
-        (rc = bring(w, a.R, nR, "resistances", &R)) || (rc = bring(w, a.pf, nP, "fixed pressures", &pf))) return rc;
+    if ((rc = bring(mem, a.ends, 2 * B, "branch ends", &ends)) || (rc = bring(mem, a.fixed, N, "fixed flags", &fixed)) ||
+        (rc = bring(mem, a.R, nR, "resistances", &R)) || (rc = bring(mem, a.pf, nP, "fixed pressures", &pf))) return rc;
     u64* ctr = nullptr;
-    FLOW_GRAB(ctr, C_PITCH, "counters");
-    SG_TRY(hipMemsetAsync(ctr, 0, C_PITCH * sizeof(u64), 0));
+    VMASK_GRAB(ctr, C_PITCH, "counters");
+    VMASK_TRY(hipMemsetAsync(ctr, 0, C_PITCH * sizeof(u64), 0));
     const u64 most = std::max(std::max(B, nR), nP);
     u64 bad = 0;
     if (most) {
         k_flow_check<<<grid_for(most, GRID_LIST), TPB>>>(ends, B, N, fixed, R, nR, pf, nP, ctr);
-        SG_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
     }
     if (bad) { vmask::set_error("the network does not fit: an end that is no node id or -1 -1, a resistance that is not finite and positive, a fixed pressure that is not finite"); return VRG_E_ARG; }
 
@@ -345,21 +294,21 @@ int flow(const Args& a) {
         derive(he, hf, N, B, t);
     } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (flow topology)"); return VRG_E_MEM; }
     G.F = t.free.size();
-    if ((rc = send(w, t.kind, "node kinds", &G.kind)) || (rc = send(w, t.anchor, "anchors", &G.anchor)) || (rc = send(w, t.part, "branch flags", &G.part)) ||
-        (rc = send(w, t.free, "free nodes", &G.free)) || (rc = send(w, t.inc_off, "incidence offsets", &G.inc_off)) ||
-        (rc = send(w, t.inc_eb, "incidence list", &G.inc_eb)) || (rc = send(w, t.inc_other, "incidence list", &G.inc_other))) return rc;
+    if ((rc = send(mem, t.kind, "node kinds", &G.kind)) || (rc = send(mem, t.anchor, "anchors", &G.anchor)) || (rc = send(mem, t.part, "branch flags", &G.part)) ||
+        (rc = send(mem, t.free, "free nodes", &G.free)) || (rc = send(mem, t.inc_off, "incidence offsets", &G.inc_off)) ||
+        (rc = send(mem, t.inc_eb, "incidence list", &G.inc_eb)) || (rc = send(mem, t.inc_other, "incidence list", &G.inc_other))) return rc;
 
     Out<double> oP, oflow, ores;
     Out<int64_t> ostatus;
-    if ((rc = oP.open(w, a.P, S * N, "node pressures")) || (rc = oflow.open(w, a.flow, S * B, "branch flows")) ||
-        (rc = ostatus.open(w, a.status, 3 * S, "scenario status")) || (rc = ores.open(w, a.residual, S, "residuals"))) return rc;
+    if ((rc = oP.open(mem, a.P, S * N, "node pressures")) || (rc = oflow.open(mem, a.flow, S * B, "branch flows")) ||
+        (rc = ostatus.open(mem, a.status, 3 * S, "scenario status")) || (rc = ores.open(mem, a.residual, S, "residuals"))) return rc;
     Space ws{nullptr, nullptr};
-    FLOW_GRAB(ws.node, S * 4 * N, "work space (nodes)"); FLOW_GRAB(ws.branch, S * 2 * B, "work space (branches)");
+    VMASK_GRAB(ws.node, S * 4 * N, "work space (nodes)"); VMASK_GRAB(ws.branch, S * 2 * B, "work space (branches)");
     const Scen sc{R, a.rs ? B : 0, pf, a.ps ? N : 0, a.k, a.tol, a.max_iter};
     const Res out{oP.dev, oflow.dev, ostatus.dev, ores.dev};
     k_flow<<<(unsigned)S, TPB>>>(G, sc, ws, out);
-    SG_TRY(hipGetLastError());
-    SG_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
     if ((rc = oP.close()) || (rc = oflow.close()) || (rc = ostatus.close()) || (rc = ores.close())) return rc;
     const int64_t counts[2] = {t.floating_components, t.floating_nodes};
     if (a.counts && (rc = put(a.counts, counts, 2))) return rc;

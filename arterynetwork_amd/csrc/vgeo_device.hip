@@ -35,6 +35,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
@@ -48,8 +49,6 @@ constexpr int32_t NO_LABEL = 0x7fffffff;
 constexpr int64_t MAX_ROUNDS = (int64_t)1 << 26;
 constexpr int C_PITCH = 32;                        // every counter keeps 256 bytes to itself
 enum { C_MASK, C_SLOTS, C_BAD, C_REACHED, C_LIST0, C_LIST1, C_N };
-
-#define VG_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 typedef unsigned long long u64;
 
@@ -345,54 +344,28 @@ __global__ void __launch_bounds__(TPB) k_geo_scatter(Geo g, u64 V, const int32_t
 
 int grid_for(u64 items, u64 cap) { return (int)std::max<u64>(1, std::min<u64>(cap, items)); }
 
-struct Work {
-    uint8_t* mask = nullptr; int64_t* seeds = nullptr; int32_t* seed_labels = nullptr; u64* ctr = nullptr; int32_t* grid = nullptr;
-    uint32_t* brick_of = nullptr; double* D = nullptr; int32_t* Lab = nullptr; uint32_t* flag = nullptr; uint32_t* list = nullptr;
-    double* dist = nullptr; int32_t* labels = nullptr;
-    ~Work() {
-        for (void* p : {(void*)mask, (void*)seeds, (void*)seed_labels, (void*)ctr, (void*)grid, (void*)brick_of, (void*)D, (void*)Lab,
-                        (void*)flag, (void*)list, (void*)dist, (void*)labels}) (void)hipFree(p);
-    }
+struct Bricks {                                                         // (names only: the call's DevMem owns them)
+    u64* ctr = nullptr; int32_t* grid = nullptr; uint32_t* brick_of = nullptr; double* D = nullptr; int32_t* Lab = nullptr;
+    uint32_t* flag = nullptr; uint32_t* list = nullptr;
 };
-
-template <class T> int dev_alloc(T** p, size_t count, const char* what) {
-    if (hipMalloc(p, std::max<size_t>(1, count) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; vmask::set_error(std::string("out of device memory (") + what + ")"); return VRG_E_MEM; }
-    return VRG_OK;
-}
-#define VG_ALLOC(p, count, what) do { int rc_ = dev_alloc(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-// a device-resident copy of a host array (or the pointer itself if it already is one)
-template <class T> int stage(const T* src, size_t count, T** own, const T** d, const char* what) {
-    if (vmask::is_device_pointer(src)) { *d = src; return VRG_OK; }
-    VG_ALLOC(*own, count, what);
-    VG_TRY(hipMemcpy(*own, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *d = *own;
-    return VRG_OK;
-}
 
 // the fixed point of one kind: rounds until no brick is flagged; flags of the first round are in flag[0 .. nslots)
 template <int LABELS>
-int iterate(Work& w, uint32_t nslots, const Geo& g, const Weights& wt, int64_t& rounds) {
+int iterate(const Bricks& b, uint32_t nslots, const Geo& g, const Weights& wt, int64_t& rounds) {
     const int glist = grid_for(((u64)nslots + TPB - 1) / TPB, 1024);
     int cur = 0;
     for (rounds = 0;; rounds++) {
         if (rounds == MAX_ROUNDS) { vmask::set_error("the relaxation did not finish"); return VRG_E_INTERNAL; }
-        u64* cursor = w.ctr + (size_t)(C_LIST0 + (int)(rounds & 1)) * C_PITCH;
-        u64* other = w.ctr + (size_t)(C_LIST0 + (int)((rounds + 1) & 1)) * C_PITCH;
-        k_geo_list<<<glist, TPB>>>(w.flag + (size_t)cur * nslots, nslots, w.list, cursor, other);
+        u64* cursor = b.ctr + (size_t)(C_LIST0 + (int)(rounds & 1)) * C_PITCH;
+        u64* other = b.ctr + (size_t)(C_LIST0 + (int)((rounds + 1) & 1)) * C_PITCH;
+        k_geo_list<<<glist, TPB>>>(b.flag + (size_t)cur * nslots, nslots, b.list, cursor, other);
         u64 active = 0;
-        VG_TRY(hipMemcpy(&active, cursor, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&active, cursor, sizeof(u64), hipMemcpyDeviceToHost));
         if (!active) break;
-        k_geo_relax<LABELS><<<(uint32_t)active, BRICK>>>(w.list, w.brick_of, w.grid, g, wt, w.D, w.Lab, w.flag + (size_t)(cur ^ 1) * nslots);
+        k_geo_relax<LABELS><<<(uint32_t)active, BRICK>>>(b.list, b.brick_of, b.grid, g, wt, b.D, b.Lab, b.flag + (size_t)(cur ^ 1) * nslots);
         cur ^= 1;
     }
-    VG_TRY(hipGetLastError());
-    return VRG_OK;
-}
-
-int put(int64_t* dst, const int64_t* src, size_t count) {              // host values to a host or device array
-    if (vmask::is_device_pointer(dst)) VG_TRY(hipMemcpy(dst, src, count * sizeof(int64_t), hipMemcpyHostToDevice));
-    else std::copy(src, src + count, dst);
+    VMASK_TRY(hipGetLastError());
     return VRG_OK;
 }
 
@@ -401,67 +374,66 @@ int geodesic(const uint8_t* mask, Geo g, const int64_t* seeds, const int32_t* se
     const u64 V = (u64)g.n0 * g.n1 * g.n2;
     const uint32_t nbricks = (uint32_t)g.B0 * (uint32_t)g.B1 * (uint32_t)g.B2;
     const bool want_labels = labels || sizes;
-    Work w;
+    DevMem mem;
+    Bricks b;
     const uint8_t* dmask; const int64_t* dseeds = nullptr; const int32_t* dseed_labels = nullptr;
-    int rc = stage(mask, V, &w.mask, &dmask, "mask");
-    if (!rc && nseed) rc = stage(seeds, (size_t)nseed, &w.seeds, &dseeds, "seeds");
-    if (!rc && nseed && seed_labels) rc = stage(seed_labels, (size_t)nseed, &w.seed_labels, &dseed_labels, "seed labels");
+    int rc = bring(mem, mask, V, "mask", &dmask);
+    if (!rc && nseed) rc = bring(mem, seeds, (size_t)nseed, "seeds", &dseeds);
+    if (!rc && nseed && seed_labels) rc = bring(mem, seed_labels, (size_t)nseed, "seed labels", &dseed_labels);
     if (rc) return rc;
     const size_t nctr = (size_t)C_N * C_PITCH + (size_t)max_label + 1;   // the counters, then sizes
-    VG_ALLOC(w.ctr, nctr, "counters");
-    VG_TRY(hipMemsetAsync(w.ctr, 0, nctr * sizeof(u64), 0));
-    u64* cnt = w.ctr + (size_t)C_N * C_PITCH;
+    VMASK_GRAB(b.ctr, nctr, "counters");
+    VMASK_TRY(hipMemsetAsync(b.ctr, 0, nctr * sizeof(u64), 0));
+    u64* cnt = b.ctr + (size_t)C_N * C_PITCH;
     if (nseed) {
-        k_geo_check<<<grid_for(((u64)nseed + TPB - 1) / TPB, 1024), TPB>>>(dseeds, dseed_labels, (u64)nseed, dmask, V, max_label, w.ctr);
+        k_geo_check<<<grid_for(((u64)nseed + TPB - 1) / TPB, 1024), TPB>>>(dseeds, dseed_labels, (u64)nseed, dmask, V, max_label, b.ctr);
         u64 bad = 0;
-        VG_TRY(hipMemcpy(&bad, w.ctr + (size_t)C_BAD * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&bad, b.ctr + (size_t)C_BAD * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
         if (bad) { vmask::set_error(std::to_string(bad) + " seeds outside the volume or the mask, or with a label outside 1..max_label"); return VRG_E_ARG; }
     }
     // the occupied bricks
-    VG_ALLOC(w.grid, nbricks, "brick grid");
-    VG_TRY(hipMemsetAsync(w.grid, 0xff, (size_t)nbricks * sizeof(int32_t), 0));            // FREE
+    VMASK_GRAB(b.grid, nbricks, "brick grid");
+    VMASK_TRY(hipMemsetAsync(b.grid, 0xff, (size_t)nbricks * sizeof(int32_t), 0));            // FREE
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(dmask) & 15u);
     const u64 nwords = (lead + V + 15u) / 16u;
-    k_geo_mark<<<grid_for((nwords + TPB - 1) / TPB, GRID_CAP), TPB>>>(reinterpret_cast<const uint4*>(dmask - lead), nwords, lead, V, g, w.grid, w.ctr);
+    k_geo_mark<<<grid_for((nwords + TPB - 1) / TPB, GRID_CAP), TPB>>>(reinterpret_cast<const uint4*>(dmask - lead), nwords, lead, V, g, b.grid, b.ctr);
     u64 nmask = 0;
-    VG_TRY(hipMemcpy(&nmask, w.ctr + (size_t)C_MASK * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&nmask, b.ctr + (size_t)C_MASK * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
     const uint32_t cap = (uint32_t)std::min<u64>(nmask, nbricks);
-    VG_ALLOC(w.brick_of, cap, "brick list");
-    k_geo_slots<<<grid_for(((u64)nbricks + TPB - 1) / TPB, GRID_CAP), TPB>>>(w.grid, nbricks, cap, w.brick_of, w.ctr);
+    VMASK_GRAB(b.brick_of, cap, "brick list");
+    k_geo_slots<<<grid_for(((u64)nbricks + TPB - 1) / TPB, GRID_CAP), TPB>>>(b.grid, nbricks, cap, b.brick_of, b.ctr);
     u64 found = 0;
-    VG_TRY(hipMemcpy(&found, w.ctr + (size_t)C_SLOTS * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&found, b.ctr + (size_t)C_SLOTS * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
     if (found > cap) { vmask::set_error("more occupied bricks than mask voxels"); return VRG_E_INTERNAL; }
     const uint32_t nslots = (uint32_t)found;
     int64_t rounds[2] = {0, 0};
     if (nslots) {
-        VG_ALLOC(w.D, (size_t)nslots * BRICK, "brick distances");
-        if (want_labels) VG_ALLOC(w.Lab, (size_t)nslots * BRICK, "brick labels");
-        VG_ALLOC(w.flag, (size_t)2 * nslots, "brick flags");
-        VG_ALLOC(w.list, nslots, "active bricks");
-        VG_TRY(hipMemsetAsync(w.flag, 0, (size_t)2 * nslots * sizeof(uint32_t), 0));
-        k_geo_init<<<nslots, BRICK>>>(dmask, g, w.brick_of, w.D, w.Lab);
+        VMASK_GRAB(b.D, (size_t)nslots * BRICK, "brick distances");
+        if (want_labels) VMASK_GRAB(b.Lab, (size_t)nslots * BRICK, "brick labels");
+        VMASK_GRAB(b.flag, (size_t)2 * nslots, "brick flags");
+        VMASK_GRAB(b.list, nslots, "active bricks");
+        VMASK_TRY(hipMemsetAsync(b.flag, 0, (size_t)2 * nslots * sizeof(uint32_t), 0));
+        k_geo_init<<<nslots, BRICK>>>(dmask, g, b.brick_of, b.D, b.Lab);
         if (nseed) {
-            k_geo_seed<<<grid_for(((u64)nseed + TPB - 1) / TPB, 1024), TPB>>>(dseeds, dseed_labels, (u64)nseed, g, w.grid, w.D, w.Lab, w.flag);
-            rc = iterate<0>(w, nslots, g, wt, rounds[0]);
+            k_geo_seed<<<grid_for(((u64)nseed + TPB - 1) / TPB, 1024), TPB>>>(dseeds, dseed_labels, (u64)nseed, g, b.grid, b.D, b.Lab, b.flag);
+            rc = iterate<0>(b, nslots, g, wt, rounds[0]);
             if (rc) return rc;
             if (want_labels) {                                          // D is final: every brick looks at its labels once, then as flagged
-                VG_TRY(hipMemsetAsync(w.flag, 0, (size_t)2 * nslots * sizeof(uint32_t), 0));
-                VG_TRY(hipMemsetAsync(w.flag, 1, (size_t)nslots * sizeof(uint32_t), 0));      // (0x01010101: not 0)
-                rc = iterate<1>(w, nslots, g, wt, rounds[1]);
+                VMASK_TRY(hipMemsetAsync(b.flag, 0, (size_t)2 * nslots * sizeof(uint32_t), 0));
+                VMASK_TRY(hipMemsetAsync(b.flag, 1, (size_t)nslots * sizeof(uint32_t), 0));      // (0x01010101: not 0)
+                rc = iterate<1>(b, nslots, g, wt, rounds[1]);
                 if (rc) return rc;
             }
         }
     }
-    double* ddist = dist; int32_t* dlab = labels;
-    if (dist && !vmask::is_device_pointer(dist)) { VG_ALLOC(w.dist, V, "dist"); ddist = w.dist; }
-    if (labels && !vmask::is_device_pointer(labels)) { VG_ALLOC(w.labels, V, "labels"); dlab = w.labels; }
-    k_geo_scatter<<<grid_for((V + TPB - 1) / TPB, GRID_CAP), TPB>>>(g, V, w.grid, w.D, w.Lab, ddist, dlab, sizes ? cnt : nullptr, w.ctr);
-    VG_TRY(hipGetLastError());
+    Out<double> odist; Out<int32_t> olab;                               // (both optional: one that is never opened keeps a null dev)
+    if ((dist && (rc = odist.open(mem, dist, V, "dist"))) || (labels && (rc = olab.open(mem, labels, V, "labels")))) return rc;
+    k_geo_scatter<<<grid_for((V + TPB - 1) / TPB, GRID_CAP), TPB>>>(g, V, b.grid, b.D, b.Lab, odist.dev, olab.dev, sizes ? cnt : nullptr, b.ctr);
+    VMASK_TRY(hipGetLastError());
     u64 reached = 0;
-    VG_TRY(hipMemcpy(&reached, w.ctr + (size_t)C_REACHED * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
-    if (w.dist) VG_TRY(hipMemcpy(dist, ddist, V * sizeof(double), hipMemcpyDeviceToHost));
-    if (w.labels) VG_TRY(hipMemcpy(labels, dlab, V * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (sizes) VG_TRY(hipMemcpy(sizes, cnt, ((size_t)max_label + 1) * sizeof(int64_t), vmask::is_device_pointer(sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&reached, b.ctr + (size_t)C_REACHED * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
+    if ((rc = odist.close()) || (rc = olab.close())) return rc;
+    if (sizes) VMASK_TRY(hipMemcpy(sizes, cnt, ((size_t)max_label + 1) * sizeof(int64_t), vmask::is_device_pointer(sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     if (counts) {
         const int64_t out[5] = {(int64_t)nmask, (int64_t)reached, (int64_t)nslots, rounds[0], rounds[1]};
         rc = put(counts, out, 5);
@@ -481,7 +453,7 @@ extern "C" int vmask_geodesic(int device, const uint8_t* mask, int64_t n0, int64
     if (rc) return rc;
     double h[3] = {1.0, 1.0, 1.0};
     if (spacing) {
-        if (vmask::is_device_pointer(spacing)) VG_TRY(hipMemcpy(h, spacing, sizeof(h), hipMemcpyDeviceToHost));
+        if (vmask::is_device_pointer(spacing)) VMASK_TRY(hipMemcpy(h, spacing, sizeof(h), hipMemcpyDeviceToHost));
         else std::copy(spacing, spacing + 3, h);
     }
     for (double x : h)

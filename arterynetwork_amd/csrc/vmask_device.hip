@@ -27,6 +27,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
@@ -47,8 +48,6 @@ template <> struct EdtWidth<long long> {
     static __device__ __forceinline__ long long ld(uint32_t g) { return (long long)g; }      // (zero-extended)
 };
 std::string g_err;
-
-#define VM_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return VRG_E_INTERNAL; } } while (0)
 
 struct Dims { int32_t n0, n1, n2; };
 
@@ -350,12 +349,12 @@ __global__ void __launch_bounds__(256) k_transpose12(const int32_t* __restrict__
 // transposed volume (two tiled transposes, ~4 GB of traffic each at 880x880x640, instead of a 20x slower pass).
 // (dist != nullptr: the distances themselves, float64, into dist - G is scratch then)
 int edt_squared(const uint8_t* dmask, Dims d, int32_t* G, double* dist = nullptr) {
+    DevMem mem;
     const size_t V = (size_t)d.n0 * d.n1 * d.n2;
     auto padded = [](size_t m) { return (m + EDT_CHUNK - 1) / EDT_CHUNK * EDT_CHUNK; };
     const size_t spill_entries = std::max((size_t)d.n0 * d.n2 * padded((size_t)d.n1), (size_t)d.n0 * d.n1 * padded((size_t)d.n2));
     int32_t* G2 = nullptr; uint2* SP = nullptr;
-    VM_TRY(hipMalloc(&G2, V * 4));
-    if (hipMalloc(&SP, spill_entries * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(G2); g_err = "out of device memory (EDT scratch)"; return VRG_E_MEM; }
+    VMASK_GRAB(G2, V, "EDT scratch"); VMASK_GRAB(SP, spill_entries, "EDT scratch");
     // (every finite squared distance, and so every square and sum of the envelope pass, below EDT_INF = 2^29; otherwise the wide
     // width: unsigned 32-bit values under the sentinel 2^32 - 1, 64-bit arithmetic)
     const bool small = (int64_t)d.n0 * d.n0 + (int64_t)d.n1 * d.n1 + (int64_t)d.n2 * d.n2 < (int64_t)EDT_INF;
@@ -375,7 +374,6 @@ int edt_squared(const uint8_t* dmask, Dims d, int32_t* G, double* dist = nullptr
     else k_transpose12<int32_t><<<tgrid, 256>>>(G2, G, d.n0, d.n2, d.n1);   // back to [n0][n1][n2]
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(G2); (void)hipFree(SP);
     if (e != hipSuccess) { g_err = std::string("EDT kernels: ") + hipGetErrorString(e); return VRG_E_INTERNAL; }
     return VRG_OK;
 }
@@ -453,7 +451,7 @@ __device__ __forceinline__ uint32_t cc_rank(CcRank k, uint32_t r) {
 }
 struct PopcU64 { __host__ __device__ uint32_t operator()(unsigned long long w) const { return (uint32_t)__builtin_popcountll(w); } };
 __global__ void __launch_bounds__(TPB) k_cc_sizes(const int32_t* __restrict__ root, CcRank rk, unsigned long long* __restrict__ sizes, uint32_t V) {
-    const int4* __restrict__ r4 = reinterpret_cast<const int4*>(root);      // (root is this library's own array: hipMalloc-aligned)
+    const int4* __restrict__ r4 = reinterpret_cast<const int4*>(root);      // (root is this library's own array: aligned as every device allocation)
     const uint32_t nq = V / 4u;
     auto count = [&](int32_t r) { if (r >= 0) atomicAdd(&sizes[cc_rank(rk, (uint32_t)r)], 1ull); };
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) { const int4 r = r4[i]; count(r.x); count(r.y); count(r.z); count(r.w); }
@@ -487,31 +485,30 @@ __global__ void __launch_bounds__(TPB) k_cc_filter(const int32_t* __restrict__ r
     if (local) atomicAdd(kept, local);
 }
 
-struct CC { int32_t* parent = nullptr; int32_t* root = nullptr; unsigned long long* bits = nullptr; uint32_t* off = nullptr; unsigned long long* sizes = nullptr; void* tmp = nullptr; uint32_t ncomp = 0;
+// (names only: the caller's DevMem owns the arrays)
+struct CC { int32_t* parent = nullptr; int32_t* root = nullptr; unsigned long long* bits = nullptr; uint32_t* off = nullptr; unsigned long long* sizes = nullptr; uint8_t* tmp = nullptr; uint32_t ncomp = 0;
             CcRank rank() const { return CcRank{bits, off}; } };
 
-void cc_free(CC& c) { (void)hipFree(c.parent); (void)hipFree(c.root); (void)hipFree(c.bits); (void)hipFree(c.off); (void)hipFree(c.sizes); (void)hipFree(c.tmp); }
-
-int cc_run(const uint8_t* dvol, Dims d, int connectivity, CC& c) {
+int cc_run(DevMem& mem, const uint8_t* dvol, Dims d, int connectivity, CC& c) {
     uint32_t V = (uint32_t)d.n0 * d.n1 * d.n2;
     const size_t nw = ((size_t)V + 63) / 64;
-    VM_TRY(hipMalloc(&c.parent, (size_t)V * 4)); VM_TRY(hipMalloc(&c.root, (size_t)V * 4)); VM_TRY(hipMalloc(&c.bits, nw * 8)); VM_TRY(hipMalloc(&c.off, nw * 4));
+    VMASK_GRAB(c.parent, V, "component parents"); VMASK_GRAB(c.root, V, "component roots"); VMASK_GRAB(c.bits, nw, "root bitmap"); VMASK_GRAB(c.off, nw, "root counts");
     k_cc_init<<<grid_for(((uint64_t)V + 3) / 4), TPB>>>(dvol, c.parent, V, (reinterpret_cast<uintptr_t>(dvol) & 3u) == 0 ? 1 : 0);
     k_cc_union<<<grid_for(V), TPB>>>(c.parent, d, connectivity);
     k_cc_flatten<<<grid_for(V), TPB>>>(c.parent, c.root, c.bits, V);
     auto counts = rocprim::make_transform_iterator(c.bits, PopcU64());
     size_t tb = 0;
-    VM_TRY(rocprim::exclusive_scan(nullptr, tb, counts, c.off, 0u, nw, rocprim::plus<uint32_t>()));
-    VM_TRY(hipMalloc(&c.tmp, tb));
-    VM_TRY(rocprim::exclusive_scan(c.tmp, tb, counts, c.off, 0u, nw, rocprim::plus<uint32_t>()));
+    VMASK_TRY(rocprim::exclusive_scan(nullptr, tb, counts, c.off, 0u, nw, rocprim::plus<uint32_t>()));
+    VMASK_GRAB(c.tmp, tb, "scan space");
+    VMASK_TRY(rocprim::exclusive_scan(c.tmp, tb, counts, c.off, 0u, nw, rocprim::plus<uint32_t>()));
     uint32_t last_off = 0; unsigned long long last_bits = 0;
-    VM_TRY(hipMemcpy(&last_off, c.off + (nw - 1), 4, hipMemcpyDeviceToHost));
-    VM_TRY(hipMemcpy(&last_bits, c.bits + (nw - 1), 8, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&last_off, c.off + (nw - 1), 4, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&last_bits, c.bits + (nw - 1), 8, hipMemcpyDeviceToHost));
     c.ncomp = last_off + (uint32_t)__builtin_popcountll(last_bits);
-    VM_TRY(hipMalloc(&c.sizes, ((size_t)c.ncomp + 1) * 8));
-    VM_TRY(hipMemset(c.sizes, 0, ((size_t)c.ncomp + 1) * 8));
+    VMASK_GRAB(c.sizes, (size_t)c.ncomp + 1, "component sizes");
+    VMASK_TRY(hipMemset(c.sizes, 0, ((size_t)c.ncomp + 1) * 8));
     k_cc_sizes<<<grid_for(((uint64_t)V + 3) / 4), TPB>>>(c.root, c.rank(), c.sizes, V);
-    VM_TRY(hipGetLastError());
+    VMASK_TRY(hipGetLastError());
     return VRG_OK;
 }
 
@@ -561,60 +558,50 @@ bool is_dev(const void* p) {
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
-// device-resident copy of an input (or the pointer itself if it already is one)
-template <class T> int stage(const T* src, size_t n, const T** d, void** owned) {
-    *owned = nullptr;
-    if (is_dev(src)) { *d = src; return VRG_OK; }
-    VM_TRY(hipMalloc(owned, n * sizeof(T)));
-    VM_TRY(hipMemcpy(*owned, src, n * sizeof(T), hipMemcpyHostToDevice));
-    *d = (const T*)*owned;
-    return VRG_OK;
-}
 template <class T> int deliver(T* dst, const T* dsrc, size_t n) {
-    VM_TRY(hipMemcpy(dst, dsrc, n * sizeof(T), hipMemcpyDefault));
+    VMASK_TRY(hipMemcpy(dst, dsrc, n * sizeof(T), hipMemcpyDefault));
     return VRG_OK;
 }
 int check(int device, int64_t n0, int64_t n1, int64_t n2, Dims& d) {
     if (n0 < 1 || n1 < 1 || n2 < 1 || (double)n0 * n1 * n2 >= 2147483000.0 || n0 > 32000 || n1 > 32000 || n2 > 32000) { g_err = "shape out of range"; return VRG_E_ARG; }
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || device < 0 || device >= cnt) { (void)hipGetLastError(); g_err = "no usable HIP device (no CPU fallback)"; return VRG_E_NOGPU; }
-    VM_TRY(hipSetDevice(device));
+    VMASK_TRY(hipSetDevice(device));
     d.n0 = (int32_t)n0; d.n1 = (int32_t)n1; d.n2 = (int32_t)n2;
     return VRG_OK;
 }
 
-template <class T> int vessel_mask_impl(const uint8_t* dbrain, const T* dves, Dims d, double edt_max, double frac1, double frac2,
+template <class T> int vessel_mask_impl(DevMem& mem, const uint8_t* dbrain, const T* dves, Dims d, double edt_max, double frac1, double frac2,
                                         int64_t min_size, uint8_t* dout, int64_t* kept) {
     size_t V = (size_t)d.n0 * d.n1 * d.n2;
     int32_t* G = nullptr;
-    VM_TRY(hipMalloc(&G, V * 4));
+    VMASK_GRAB(G, V, "squared distances");
     int rc = edt_squared(dbrain, d, G);                            // distance_transform_edt(brainVolumeMask) :183
-    if (rc) { (void)hipFree(G); return rc; }
+    if (rc) return rc;
     const int nb = 1024;
     T* mm = nullptr;
-    VM_TRY(hipMalloc(&mm, (2 + 2 * nb) * sizeof(T)));
+    VMASK_GRAB(mm, 2 + 2 * nb, "extrema");
     k_minmax<T><<<nb, TPB>>>(dves, V, mm, (reinterpret_cast<uintptr_t>(dves) & 15u) == 0 ? 1 : 0);
     std::vector<T> h(2 + 2 * nb);
-    VM_TRY(hipMemcpy(h.data(), mm, h.size() * sizeof(T), hipMemcpyDeviceToHost));
-    (void)hipFree(mm);
+    VMASK_TRY(hipMemcpy(h.data(), mm, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+    mem.drop(mm);
     T lo = h[2], hi = h[3];                                        // np.amin / np.amax :187
     for (int b = 1; b < nb; b++) { lo = std::min(lo, h[2 + 2 * b]); hi = std::max(hi, h[3 + 2 * b]); }
     // numpy scalar arithmetic in the volume's dtype (float32 stays float32 under NEP 50)
     T thr1 = lo + (T)frac1 * (hi - lo), thr2 = lo + (T)frac2 * (hi - lo);
     uint8_t* fg = nullptr;
-    VM_TRY(hipMalloc(&fg, V));
+    VMASK_GRAB(fg, V, "foreground");
     k_threshold<T><<<grid_for(V), TPB>>>(dves, G, edt_max, thr1, thr2, fg, V);
-    (void)hipFree(G);
+    mem.drop(G);
     CC c;
-    rc = cc_run(fg, d, 3, c);                                      // labelVolume(..., maxHop=3) :195
-    if (rc) { cc_free(c); (void)hipFree(fg); return rc; }
+    rc = cc_run(mem, fg, d, 3, c);                                 // labelVolume(..., maxHop=3) :195
+    if (rc) return rc;
     unsigned long long* dk = nullptr;
-    VM_TRY(hipMalloc(&dk, 8)); VM_TRY(hipMemset(dk, 0, 8));
+    VMASK_GRAB(dk, 1, "kept count"); VMASK_TRY(hipMemset(dk, 0, 8));
     k_cc_filter<<<grid_for(((uint64_t)V + 3) / 4), TPB>>>(c.root, c.rank(), c.sizes, (unsigned long long)min_size, dout, dk, (uint32_t)V, (reinterpret_cast<uintptr_t>(dout) & 3u) == 0 ? 1 : 0);
     unsigned long long k = 0;
-    VM_TRY(hipMemcpy(&k, dk, 8, hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&k, dk, 8, hipMemcpyDeviceToHost));
     if (kept) *kept = (int64_t)k;
-    (void)hipFree(dk); (void)hipFree(fg); cc_free(c);
     return VRG_OK;
 }
 
@@ -636,18 +623,18 @@ int vmask_edt(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n
     int rc = check(device, n0, n1, n2, d);
     if (rc) return rc;
     size_t V = (size_t)n0 * n1 * n2;
-    const uint8_t* dm; void* own;
-    rc = stage(mask, V, &dm, &own);
+    DevMem mem;
+    const uint8_t* dm = nullptr;
+    rc = bring(mem, mask, V, "mask", &dm);
     if (rc) return rc;
     int32_t* G = nullptr; double* dout = nullptr;
-    VM_TRY(hipMalloc(&G, V * 4));
+    VMASK_GRAB(G, V, "squared distances");
     const bool od = is_dev(out);
     if (od) dout = out;
-    else if (hipMalloc(&dout, V * 8) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(G); if (own) (void)hipFree(own); g_err = "out of device memory (EDT output)"; return VRG_E_MEM; }
+    else VMASK_GRAB(dout, V, "EDT output");
     rc = edt_squared(dm, d, G, dout);                                  // (the last transpose writes the roots: synchronised inside)
     if (!rc && !od) rc = deliver(out, (const double*)dout, V);
-    if (!od) (void)hipFree(dout);
-    (void)hipFree(G); if (own) (void)hipFree(own);
+    if (!od) mem.drop(dout);
     return rc;
 }
 
@@ -658,25 +645,26 @@ int vmask_label(int device, const uint8_t* volume, int64_t n0, int64_t n1, int64
     int rc = check(device, n0, n1, n2, d);
     if (rc) return rc;
     size_t V = (size_t)n0 * n1 * n2;
-    const uint8_t* dv; void* own;
-    rc = stage(volume, V, &dv, &own);
+    DevMem mem;
+    const uint8_t* dv = nullptr;
+    rc = bring(mem, volume, V, "volume", &dv);
     if (rc) return rc;
     CC c;
-    rc = cc_run(dv, d, connectivity, c);
+    rc = cc_run(mem, dv, d, connectivity, c);
     if (!rc) {
         bool od = is_dev(labels);
-        int32_t* dl = labels;
-        if (!od) VM_TRY(hipMalloc(&dl, V * 4));
+        int32_t* dl = nullptr;
+        if (od) dl = labels;
+        else VMASK_GRAB(dl, V, "labels");
         k_cc_labels<<<grid_for(((uint64_t)V + 3) / 4), TPB>>>(c.root, c.rank(), dl, (uint32_t)V, (reinterpret_cast<uintptr_t>(dl) & 15u) == 0 ? 1 : 0);
-        if (!od) { rc = deliver(labels, (const int32_t*)dl, V); (void)hipFree(dl); }
-        else VM_TRY(hipDeviceSynchronize());
+        if (!od) { rc = deliver(labels, (const int32_t*)dl, V); mem.drop(dl); }
+        else VMASK_TRY(hipDeviceSynchronize());
         if (n) *n = c.ncomp;
         if (!rc && sizes) {
             if (cap < (int64_t)c.ncomp) { g_err = "sizes buffer too small"; rc = VRG_E_ARG; }
-            else if (c.ncomp) VM_TRY(hipMemcpy(sizes, c.sizes, (size_t)c.ncomp * 8, hipMemcpyDeviceToHost));
+            else if (c.ncomp) VMASK_TRY(hipMemcpy(sizes, c.sizes, (size_t)c.ncomp * 8, hipMemcpyDeviceToHost));
         }
     }
-    cc_free(c); if (own) (void)hipFree(own);
     return rc;
 }
 
@@ -687,18 +675,17 @@ int vmask_vessel_mask(int device, const uint8_t* brainMask, const void* vesselne
     int rc = check(device, n0, n1, n2, d);
     if (rc) return rc;
     size_t V = (size_t)n0 * n1 * n2;
-    const uint8_t* db; void* ownb;
-    rc = stage(brainMask, V, &db, &ownb);
+    DevMem mem;
+    const uint8_t* db = nullptr;
+    rc = bring(mem, brainMask, V, "brain mask", &db);
     if (rc) return rc;
     bool od = is_dev(out);
-    uint8_t* dout = out;
-    if (!od) VM_TRY(hipMalloc(&dout, V));
-    void* ownv = nullptr;
-    if (dtype == VRG_F32) { const float* dv; rc = stage((const float*)vesselness, V, &dv, &ownv); if (!rc) rc = vessel_mask_impl<float>(db, dv, d, edt_max, frac1, frac2, min_size, dout, kept); }
-    else { const double* dv; rc = stage((const double*)vesselness, V, &dv, &ownv); if (!rc) rc = vessel_mask_impl<double>(db, dv, d, edt_max, frac1, frac2, min_size, dout, kept); }
+    uint8_t* dout = nullptr;
+    if (od) dout = out;
+    else VMASK_GRAB(dout, V, "vessel mask");
+    if (dtype == VRG_F32) { const float* dv; rc = bring(mem, (const float*)vesselness, V, "vesselness", &dv); if (!rc) rc = vessel_mask_impl<float>(mem, db, dv, d, edt_max, frac1, frac2, min_size, dout, kept); }
+    else { const double* dv; rc = bring(mem, (const double*)vesselness, V, "vesselness", &dv); if (!rc) rc = vessel_mask_impl<double>(mem, db, dv, d, edt_max, frac1, frac2, min_size, dout, kept); }
     if (!rc && !od) rc = deliver(out, (const uint8_t*)dout, V);
-    if (!od) (void)hipFree(dout);
-    if (ownb) (void)hipFree(ownb); if (ownv) (void)hipFree(ownv);
     return rc;
 }
 

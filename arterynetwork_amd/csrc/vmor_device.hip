@@ -33,6 +33,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 #include "vseg_slots.h"
 
 #pragma clang fp contract(off)
@@ -269,41 +270,6 @@ __global__ void __launch_bounds__(TPB) k_mor_finish(const int64_t* __restrict__ 
     }
 }
 
-struct Work {
-    std::vector<void*> owned;
-    ~Work() { for (void* p : owned) (void)hipFree(p); }
-    template <class T> int grab(T** p, size_t count, const char* what) {
-        const int rc = dev_alloc(p, count, what);
-        if (!rc) owned.push_back(*p);
-        return rc;
-    }
-};
-#define MOR_GRAB(p, count, what) do { int rc_ = w.grab(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-// a caller's array that the kernels read: itself when it lives on the device, a device copy otherwise
-template <class T> int bring(Work& w, const T* p, size_t n, const char* what, const T** dev) {
-    if (!n || vmask::is_device_pointer(p)) { *dev = p; return VRG_OK; }
-    T* d = nullptr;
-    const int rc = w.grab(&d, n, what);
-    if (rc) return rc;
-    SG_TRY(hipMemcpy(d, p, n * sizeof(T), hipMemcpyHostToDevice));
-    *dev = d;
-    return VRG_OK;
-}
-// a caller's array that the kernels write: itself when it lives on the device, a device copy otherwise
-template <class T> struct Out {
-    T* user = nullptr; T* dev = nullptr; size_t count = 0;
-    int open(Work& w, T* p, size_t n, const char* what) {
-        user = p; count = n;
-        if (vmask::is_device_pointer(p)) { dev = p; return VRG_OK; }
-        return w.grab(&dev, n, what);
-    }
-    int close() {
-        if (dev != user && count) SG_TRY(hipMemcpy(user, dev, count * sizeof(T), hipMemcpyDeviceToHost));
-        return VRG_OK;
-    }
-};
-
 struct Args {
     const double* dist; const int64_t* offsets; int64_t B; const int64_t* voxels; const int64_t* ends; const int64_t* nodevox; int64_t N;
     const int64_t* roots; int64_t nroots; int64_t local_steps;
@@ -318,58 +284,58 @@ inline double length_of(const int64_t* o, const double* h) {
 
 int morphometry(const Args& g, const Vol& s, const double* h) {
     const u64 B = (u64)g.B, N = (u64)g.N, R = (u64)g.nroots;
-    Work w;
+    DevMem mem;
     int rc;
     int64_t total = 0;
     if (B) {
         int64_t edge[2] = {0, 0};
         if (vmask::is_device_pointer(g.offsets)) {
-            SG_TRY(hipMemcpy(&edge[0], g.offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
-            SG_TRY(hipMemcpy(&edge[1], g.offsets + B, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&edge[0], g.offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&edge[1], g.offsets + B, sizeof(int64_t), hipMemcpyDeviceToHost));
         } else { edge[0] = g.offsets[0]; edge[1] = g.offsets[B]; }
         if (edge[0] != 0 || edge[1] < 2 * (int64_t)B || edge[1] > ((int64_t)1 << 40)) { vmask::set_error("offsets do not describe branches of at least two entries"); return VRG_E_ARG; }
         total = edge[1];
     }
     const int64_t* off = nullptr; const int64_t* vox = nullptr; const int64_t* ends = nullptr; const int64_t* nodevox = nullptr; const int64_t* roots = nullptr;
     const double* dist = nullptr;
-    if ((rc = bring(w, g.offsets, B ? B + 1 : 0, "offsets", &off)) || (rc = bring(w, g.voxels, (size_t)total, "branch voxels", &vox)) ||
-        (rc = bring(w, g.ends, 2 * B, "branch ends", &ends)) || (rc = bring(w, g.nodevox, N, "node voxels", &nodevox)) ||
-        (rc = bring(w, g.roots, R, "roots", &roots)) || (rc = bring(w, g.dist, (size_t)s.V, "distance volume", &dist))) return rc;
+    if ((rc = bring(mem, g.offsets, B ? B + 1 : 0, "offsets", &off)) || (rc = bring(mem, g.voxels, (size_t)total, "branch voxels", &vox)) ||
+        (rc = bring(mem, g.ends, 2 * B, "branch ends", &ends)) || (rc = bring(mem, g.nodevox, N, "node voxels", &nodevox)) ||
+        (rc = bring(mem, g.roots, R, "roots", &roots)) || (rc = bring(mem, g.dist, (size_t)s.V, "distance volume", &dist))) return rc;
     u64* ctr = nullptr;
-    MOR_GRAB(ctr, 2 * C_PITCH, "counters");
-    SG_TRY(hipMemsetAsync(ctr, 0, 2 * C_PITCH * sizeof(u64), 0));
+    VMASK_GRAB(ctr, 2 * C_PITCH, "counters");
+    VMASK_TRY(hipMemsetAsync(ctr, 0, 2 * C_PITCH * sizeof(u64), 0));
     const u64 most = std::max(std::max(B, (u64)total), std::max(N, R));
     u64 bad = 0;
     if (most) {
         k_mor_check<<<grid_for(most, GRID_LIST), TPB>>>(off, B, vox, (u64)total, s.V, ends, nodevox, N, roots, R, ctr);
-        SG_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
     }
     if (bad) { vmask::set_error("the branch table does not fit the volume: offsets, voxels, ends, node voxels or roots out of range"); return VRG_E_ARG; }
 
     Out<int64_t> obi, oinc, odepth, olevel;
     Out<double> obf, orad, odist, oentry;
-    if ((rc = obi.open(w, g.bi, B * BI_N, "branch integers")) || (rc = obf.open(w, g.bf, B * BF_N, "branch sums")) ||
-        (rc = orad.open(w, g.radius, N, "node radii")) || (rc = oinc.open(w, g.incident, 3 * N, "incident branches"))) return rc;
+    if ((rc = obi.open(mem, g.bi, B * BI_N, "branch integers")) || (rc = obf.open(mem, g.bf, B * BF_N, "branch sums")) ||
+        (rc = orad.open(mem, g.radius, N, "node radii")) || (rc = oinc.open(mem, g.incident, 3 * N, "incident branches"))) return rc;
     if (B) k_mor_branch<<<grid_for(16 * B, 4 * GRID_LIST), TPB>>>(off, B, vox, dist, s, g.local_steps, obi.dev, obf.dev);
     if (g.entry_radius && total) {
-        if ((rc = oentry.open(w, g.entry_radius, (size_t)total, "entry radii"))) return rc;
+        if ((rc = oentry.open(mem, g.entry_radius, (size_t)total, "entry radii"))) return rc;
         k_mor_gather<<<grid_for((u64)total, 4 * GRID_LIST), TPB>>>(vox, (u64)total, dist, oentry.dev);
     }
     if (N) {
         Incident t{nullptr, nullptr, nullptr, nullptr};
-        MOR_GRAB(t.deg, N, "end counts"); MOR_GRAB(t.lo, N, "incident ends"); MOR_GRAB(t.hi, N, "incident ends"); MOR_GRAB(t.sum, N, "incident ends");
-        SG_TRY(hipMemsetAsync(t.deg, 0, N * sizeof(uint32_t), 0)); SG_TRY(hipMemsetAsync(t.lo, 0xff, N * sizeof(u64), 0));
-        SG_TRY(hipMemsetAsync(t.hi, 0, N * sizeof(u64), 0)); SG_TRY(hipMemsetAsync(t.sum, 0, N * sizeof(u64), 0));
+        VMASK_GRAB(t.deg, N, "end counts"); VMASK_GRAB(t.lo, N, "incident ends"); VMASK_GRAB(t.hi, N, "incident ends"); VMASK_GRAB(t.sum, N, "incident ends");
+        VMASK_TRY(hipMemsetAsync(t.deg, 0, N * sizeof(uint32_t), 0)); VMASK_TRY(hipMemsetAsync(t.lo, 0xff, N * sizeof(u64), 0));
+        VMASK_TRY(hipMemsetAsync(t.hi, 0, N * sizeof(u64), 0)); VMASK_TRY(hipMemsetAsync(t.sum, 0, N * sizeof(u64), 0));
         if (B) k_mor_incident<<<grid_for(2 * B, GRID_LIST), TPB>>>(ends, B, N, t);
         k_mor_node<<<grid_for(N, GRID_LIST), TPB>>>(nodevox, N, dist, t, orad.dev, oinc.dev);
     }
-    SG_TRY(hipGetLastError());
+    VMASK_TRY(hipGetLastError());
     // the path lengths: on the host from the integer counts, in the stated order, and back for the depth
     if (B) try {
         std::vector<int64_t> hbi(B * BI_N);
         std::vector<double> hbf(B * BF_N);
-        SG_TRY(hipMemcpy(hbi.data(), obi.dev, hbi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-        SG_TRY(hipMemcpy(hbf.data(), obf.dev, hbf.size() * sizeof(double), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hbi.data(), obi.dev, hbi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hbf.data(), obf.dev, hbf.size() * sizeof(double), hipMemcpyDeviceToHost));
         double wc[7];
         for (int c = 0; c < 7; c++) {
             const int64_t o[3] = {((c + 1) >> 2) & 1, ((c + 1) >> 1) & 1, (c + 1) & 1};
@@ -383,7 +349,7 @@ int morphometry(const Args& g, const Vol& s, const double* h) {
             len = len + length_of(o + BI_JUMP_OFFSET + 3, h);
             hbf[b * BF_N + BF_PATH] = len;
         }
-        if (obf.dev == obf.user || R) SG_TRY(hipMemcpy(obf.dev, hbf.data(), hbf.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (obf.dev == obf.user || R) VMASK_TRY(hipMemcpy(obf.dev, hbf.data(), hbf.size() * sizeof(double), hipMemcpyHostToDevice));
         if (obi.dev != obi.user) std::copy(hbi.begin(), hbi.end(), obi.user);
         if (obf.dev != obf.user) std::copy(hbf.begin(), hbf.end(), obf.user);
     } catch (const std::bad_alloc&) { vmask::set_error("out of host memory (branch tables)"); return VRG_E_MEM; }
@@ -391,39 +357,39 @@ int morphometry(const Args& g, const Vol& s, const double* h) {
 
     int64_t rounds[2] = {0, 0};
     if (R) {
-        if ((rc = odist.open(w, g.distance, N, "path distances")) || (rc = odepth.open(w, g.depth, 3 * N, "node depths")) ||
-            (rc = olevel.open(w, g.level, B, "branch levels"))) return rc;
+        if ((rc = odist.open(mem, g.distance, N, "path distances")) || (rc = odepth.open(mem, g.depth, 3 * N, "node depths")) ||
+            (rc = olevel.open(mem, g.level, B, "branch levels"))) return rc;
         u64* D = reinterpret_cast<u64*>(odist.dev);
         int32_t* stamp = nullptr;
-        MOR_GRAB(stamp, N, "level stamps");
+        VMASK_GRAB(stamp, N, "level stamps");
         const int gn = grid_for(N, GRID_LIST), gb = grid_for(B, GRID_LIST);
         k_mor_fill<<<gn, TPB>>>(D, N);
-        SG_TRY(hipMemsetAsync(odepth.dev, 0xff, 3 * N * sizeof(int64_t), 0));
-        SG_TRY(hipMemsetAsync(stamp, 0x7f, N * sizeof(int32_t), 0));
+        VMASK_TRY(hipMemsetAsync(odepth.dev, 0xff, 3 * N * sizeof(int64_t), 0));
+        VMASK_TRY(hipMemsetAsync(stamp, 0x7f, N * sizeof(int32_t), 0));
         k_mor_roots<<<grid_for(R, GRID_LIST), TPB>>>(roots, R, N, D, odepth.dev, stamp);
         const int64_t limit = std::max<int64_t>((int64_t)N, 1);
         for (u64 lowered = 1; B && lowered;) {
             if (rounds[0] == limit) { vmask::set_error("the path distances did not settle within one round per node"); return VRG_E_INTERNAL; }
-            SG_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
+            VMASK_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
             k_mor_relax<<<gb, TPB>>>(ends, obf.dev, B, N, D, ctr);
-            SG_TRY(hipMemcpy(&lowered, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&lowered, ctr, sizeof(u64), hipMemcpyDeviceToHost));
             rounds[0]++;
         }
         if (B) k_mor_parent<<<gb, TPB>>>(ends, obf.dev, B, N, D, odepth.dev);
         for (u64 set = 1; B && set;) {
             if (rounds[1] == limit) { vmask::set_error("the depth levels did not settle within one round per node"); return VRG_E_INTERNAL; }
-            SG_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
+            VMASK_TRY(hipMemsetAsync(ctr, 0, sizeof(u64), 0));
             k_mor_level<<<gn, TPB>>>(ends, off, B, N, (int32_t)(rounds[1] + 1), odepth.dev, stamp, ctr);
-            SG_TRY(hipMemcpy(&set, ctr, sizeof(u64), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&set, ctr, sizeof(u64), hipMemcpyDeviceToHost));
             rounds[1]++;
         }
         if (B) k_mor_finish<<<gb, TPB>>>(ends, B, N, odepth.dev, olevel.dev);
-        SG_TRY(hipGetLastError());
+        VMASK_TRY(hipGetLastError());
         if ((rc = odist.close()) || (rc = odepth.close()) || (rc = olevel.close())) return rc;
     }
     if (g.counts && (rc = put(g.counts, rounds, 2))) return rc;
-    SG_TRY(hipGetLastError());
-    SG_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
     return VRG_OK;
 }
 
@@ -445,7 +411,7 @@ extern "C" int vmask_morphometry(int device, int64_t n0, int64_t n1, int64_t n2,
     if (rc) return rc;
     double h[3] = {1.0, 1.0, 1.0};
     if (spacing) {
-        if (vmask::is_device_pointer(spacing)) SG_TRY(hipMemcpy(h, spacing, sizeof(h), hipMemcpyDeviceToHost));
+        if (vmask::is_device_pointer(spacing)) VMASK_TRY(hipMemcpy(h, spacing, sizeof(h), hipMemcpyDeviceToHost));
         else std::copy(spacing, spacing + 3, h);
     }
     for (double x : h)

@@ -39,6 +39,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 #include "vseg_slots.h"
 
 namespace {
@@ -207,35 +208,29 @@ __global__ void __launch_bounds__(TPB) k_seg_scatter(const uint32_t* __restrict_
     }
 }
 
-struct Work {
-    uint8_t* in = nullptr; u64* ctr = nullptr; uint32_t* list = nullptr; u64* tab = nullptr; uint32_t* word = nullptr; uint32_t* nbr = nullptr;
+struct Buffers {                                                        // (names only: the call's DevMem owns them)
+    u64* ctr = nullptr; uint32_t* list = nullptr; u64* tab = nullptr; uint32_t* word = nullptr; uint32_t* nbr = nullptr;
     uint4* st[2] = {nullptr, nullptr}; uint4* info = nullptr; uint32_t* tail = nullptr;
     u64* keys[2] = {nullptr, nullptr}; uint32_t* lens = nullptr; int64_t* off = nullptr; int64_t* vox = nullptr;
-    ~Work() {
-        for (void* p : {(void*)in, (void*)ctr, (void*)list, (void*)tab, (void*)word, (void*)nbr, (void*)st[0], (void*)st[1], (void*)info, (void*)tail,
-                        (void*)keys[0], (void*)keys[1], (void*)lens, (void*)off, (void*)vox}) (void)hipFree(p);
-    }
 };
 
 int segments(const uint8_t* skeleton, Dim d, int64_t* counts, int64_t* offsets, int64_t cap_seg, int64_t* voxels, int64_t cap_vox) {
     const u64 V = (u64)d.n0 * d.n1 * d.n2;
     const bool want = offsets != nullptr;
-    Work w;
-    const uint8_t* vol = skeleton;
-    if (!vmask::is_device_pointer(skeleton)) {
-        SG_ALLOC(w.in, V, "volume");
-        SG_TRY(hipMemcpy(w.in, skeleton, V, hipMemcpyHostToDevice));
-        vol = w.in;
-    }
-    SG_ALLOC(w.ctr, (size_t)C_N * C_PITCH, "counters");
-    SG_TRY(hipMemsetAsync(w.ctr, 0, (size_t)C_N * C_PITCH * sizeof(u64), 0));
+    DevMem mem;
+    Buffers b;
+    const uint8_t* vol = nullptr;
+    int rc = bring(mem, skeleton, V, "volume", &vol);
+    if (rc) return rc;
+    VMASK_GRAB(b.ctr, (size_t)C_N * C_PITCH, "counters");
+    VMASK_TRY(hipMemsetAsync(b.ctr, 0, (size_t)C_N * C_PITCH * sizeof(u64), 0));
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(vol) & 15u);
     const uint4* base = reinterpret_cast<const uint4*>(vol - lead);
     const u64 nwords = (lead + V + 15u) / 16u;
     const int gvol = grid_for(nwords, GRID_VOLUME);
-    k_seg_count<<<gvol, TPB>>>(base, nwords, lead, V, w.ctr + c_at(C_OBJ));
+    k_seg_count<<<gvol, TPB>>>(base, nwords, lead, V, b.ctr + c_at(C_OBJ));
     u64 nobj = 0;
-    SG_TRY(hipMemcpy(&nobj, w.ctr + c_at(C_OBJ), sizeof(u64), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(&nobj, b.ctr + c_at(C_OBJ), sizeof(u64), hipMemcpyDeviceToHost));
     int64_t out[5] = {0, 0, 0, 0, 0};
     if (nobj >= (1ull << 30)) { vmask::set_error("more than 2^30 object voxels"); return VRG_E_ARG; }
     const uint32_t n = (uint32_t)nobj, nd = 2u * n;
@@ -245,52 +240,52 @@ int segments(const uint8_t* skeleton, Dim d, int64_t* counts, int64_t* offsets, 
     if (n) {
         const int bits = hash_bits(n);
         h.mask = (uint32_t)((1ull << bits) - 1ull); h.shift = 32u - (uint32_t)bits;
-        SG_ALLOC(w.tab, (size_t)1 << bits, "index table");
-        h.tab = w.tab;
-        SG_ALLOC(w.list, n, "voxel list"); SG_ALLOC(w.word, n, "neighbourhoods"); SG_ALLOC(w.nbr, nd, "neighbours");
-        SG_ALLOC(w.st[0], nd, "darts"); SG_ALLOC(w.st[1], nd, "darts"); SG_ALLOC(w.info, n, "segment keys"); SG_ALLOC(w.tail, n, "segment ends");
-        SG_TRY(hipMemsetAsync(w.tab, 0xff, ((size_t)1 << bits) * sizeof(u64), 0));
-        SG_TRY(hipMemsetAsync(w.nbr, 0xff, (size_t)nd * sizeof(uint32_t), 0));
+        VMASK_GRAB(b.tab, (size_t)1 << bits, "index table");
+        h.tab = b.tab;
+        VMASK_GRAB(b.list, n, "voxel list"); VMASK_GRAB(b.word, n, "neighbourhoods"); VMASK_GRAB(b.nbr, nd, "neighbours");
+        VMASK_GRAB(b.st[0], nd, "darts"); VMASK_GRAB(b.st[1], nd, "darts"); VMASK_GRAB(b.info, n, "segment keys"); VMASK_GRAB(b.tail, n, "segment ends");
+        VMASK_TRY(hipMemsetAsync(b.tab, 0xff, ((size_t)1 << bits) * sizeof(u64), 0));
+        VMASK_TRY(hipMemsetAsync(b.nbr, 0xff, (size_t)nd * sizeof(uint32_t), 0));
         const int gslot = grid_for(n, GRID_LIST), gdart = grid_for(nd, GRID_LIST);
-        k_seg_compact<<<gvol, TPB>>>(base, nwords, lead, V, n, w.list, h, w.ctr + c_at(C_CURSOR));
-        k_seg_gather<<<gslot, TPB>>>(vol, d, w.list, n, w.word, w.nbr, w.ctr);
-        k_seg_link<<<gdart, TPB>>>(w.list, w.word, w.nbr, n, h, w.st[0], w.ctr);
+        k_seg_compact<<<gvol, TPB>>>(base, nwords, lead, V, n, b.list, h, b.ctr + c_at(C_CURSOR));
+        k_seg_gather<<<gslot, TPB>>>(vol, d, b.list, n, b.word, b.nbr, b.ctr);
+        k_seg_link<<<gdart, TPB>>>(b.list, b.word, b.nbr, n, h, b.st[0], b.ctr);
         u64 open = 0;
-        SG_TRY(hipMemcpy(&open, w.ctr + c_at(C_OPEN), sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&open, b.ctr + c_at(C_OPEN), sizeof(u64), hipMemcpyDeviceToHost));
         while (open) {                                                  // until every dart is at a terminal or on a ring that knows its minimum
             if (rounds == MAX_ROUNDS) { vmask::set_error("pointer jumping did not finish"); return VRG_E_INTERNAL; }
-            u64* c = w.ctr + c_at(C_ROUND + 2 * rounds);
-            k_seg_jump<<<gdart, TPB>>>(w.st[cur], w.st[cur ^ 1], nd, c, c + C_PITCH);
+            u64* c = b.ctr + c_at(C_ROUND + 2 * rounds);
+            k_seg_jump<<<gdart, TPB>>>(b.st[cur], b.st[cur ^ 1], nd, c, c + C_PITCH);
             u64 hc[C_PITCH + 1];
-            SG_TRY(hipMemcpy(hc, c, sizeof(hc), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(hc, c, sizeof(hc), hipMemcpyDeviceToHost));
             cur ^= 1; rounds++;
             open = hc[0];
             if (!hc[C_PITCH]) break;
         }
-        k_seg_resolve<<<gslot, TPB>>>(w.list, w.word, w.nbr, n, d, h, w.st[cur], w.info, w.tail, w.ctr);
+        k_seg_resolve<<<gslot, TPB>>>(b.list, b.word, b.nbr, n, d, h, b.st[cur], b.info, b.tail, b.ctr);
         u64 hc[(C_TOTAL - C_NODE) * C_PITCH + 1];
-        SG_TRY(hipMemcpy(hc, w.ctr + c_at(C_NODE), sizeof(hc), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(hc, b.ctr + c_at(C_NODE), sizeof(hc), hipMemcpyDeviceToHost));
         nseg = hc[c_at(C_SEG - C_NODE)]; total = hc[c_at(C_TOTAL - C_NODE)];
         out[2] = (int64_t)hc[0]; out[3] = (int64_t)hc[c_at(C_ISO - C_NODE)];
     }
     out[0] = (int64_t)nseg; out[1] = (int64_t)total; out[4] = rounds;
-    int rc = put(counts, out, 5);
+    rc = put(counts, out, 5);
     if (rc || !want) return rc;
     if ((u64)cap_seg < nseg || (u64)cap_vox < total) { vmask::set_error("capacity too small (the needed sizes are in counts)"); return VRG_E_ARG; }
     if (!nseg) { const int64_t zero = 0; return put(offsets, &zero, 1); }
     if (nseg >= (1ull << 31)) { vmask::set_error("more than 2^31 segments"); return VRG_E_ARG; }
-    SG_ALLOC(w.keys[0], nseg, "segment heads"); SG_ALLOC(w.keys[1], nseg, "segment heads");
-    SG_ALLOC(w.lens, nseg, "segment heads");
+    VMASK_GRAB(b.keys[0], nseg, "segment heads"); VMASK_GRAB(b.keys[1], nseg, "segment heads");
+    VMASK_GRAB(b.lens, nseg, "segment heads");
     int64_t* doff = offsets; int64_t* dvox = voxels;
-    if (!vmask::is_device_pointer(offsets)) { SG_ALLOC(w.off, nseg + 1, "offsets"); doff = w.off; }
-    if (!vmask::is_device_pointer(voxels)) { SG_ALLOC(w.vox, total, "segment voxels"); dvox = w.vox; }
+    if (!vmask::is_device_pointer(offsets)) { VMASK_GRAB(b.off, nseg + 1, "offsets"); doff = b.off; }
+    if (!vmask::is_device_pointer(voxels)) { VMASK_GRAB(b.vox, total, "segment voxels"); dvox = b.vox; }
     const int gslot = grid_for(n, GRID_LIST);
-    k_seg_heads<<<gslot, TPB>>>(w.list, w.word, n, d, w.info, nseg, w.keys[0], w.lens, w.ctr);
+    k_seg_heads<<<gslot, TPB>>>(b.list, b.word, n, d, b.info, nseg, b.keys[0], b.lens, b.ctr);
     // the heads alone go to the host: sorted by key there, their lengths summed into the offsets
     std::vector<u64> hkeys(nseg);
     std::vector<uint32_t> hlens(nseg);
-    SG_TRY(hipMemcpy(hkeys.data(), w.keys[0], nseg * sizeof(u64), hipMemcpyDeviceToHost));
-    SG_TRY(hipMemcpy(hlens.data(), w.lens, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(hkeys.data(), b.keys[0], nseg * sizeof(u64), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(hlens.data(), b.lens, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::vector<std::pair<u64, uint32_t>> heads(nseg);
     for (size_t k = 0; k < nseg; k++) heads[k] = {hkeys[k], hlens[k]};
     std::sort(heads.begin(), heads.end());
@@ -298,13 +293,13 @@ int segments(const uint8_t* skeleton, Dim d, int64_t* counts, int64_t* offsets, 
     hoff[0] = 0;
     for (size_t k = 0; k < nseg; k++) { hkeys[k] = heads[k].first; hoff[k + 1] = hoff[k] + heads[k].second; }
     if ((u64)hoff[nseg] != total) { vmask::set_error("segment lengths do not add up"); return VRG_E_INTERNAL; }
-    SG_TRY(hipMemcpy(w.keys[1], hkeys.data(), nseg * sizeof(u64), hipMemcpyHostToDevice));
-    SG_TRY(hipMemcpy(doff, hoff.data(), (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    k_seg_scatter<<<gslot, TPB>>>(w.list, w.word, n, d, w.info, w.tail, w.keys[1], doff, nseg, total, dvox);
-    SG_TRY(hipGetLastError());
-    if (w.off) std::copy(hoff.begin(), hoff.end(), offsets);
-    if (w.vox) SG_TRY(hipMemcpy(voxels, dvox, total * sizeof(int64_t), hipMemcpyDeviceToHost));
-    SG_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipMemcpy(b.keys[1], hkeys.data(), nseg * sizeof(u64), hipMemcpyHostToDevice));
+    VMASK_TRY(hipMemcpy(doff, hoff.data(), (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    k_seg_scatter<<<gslot, TPB>>>(b.list, b.word, n, d, b.info, b.tail, b.keys[1], doff, nseg, total, dvox);
+    VMASK_TRY(hipGetLastError());
+    if (b.off) std::copy(hoff.begin(), hoff.end(), offsets);
+    if (b.vox) VMASK_TRY(hipMemcpy(voxels, dvox, total * sizeof(int64_t), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipDeviceSynchronize());
     return VRG_OK;
 }
 

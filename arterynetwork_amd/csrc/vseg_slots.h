@@ -1,7 +1,7 @@
 // vseg_slots.h - what the passes over the compacted object voxels ("slots") share: vseg_device.hip (segment tracing) and
 // vbr_device.hip (branch graph).  The volume is read as a flat byte string in aligned 16-byte words, its object voxels are
-// counted, listed (one atomic per wave) and entered idx -> slot into an open-addressing hash table; the wave helpers, the
-// 27-bit neighbourhood numbering and the allocation helpers of those translation units.  Everything has internal linkage.
+// counted, listed (one atomic per wave) and entered idx -> slot into an open-addressing hash table; the wave helpers and the
+// 27-bit neighbourhood numbering of those translation units (their host-side helpers: vmask_host.h).  Everything has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,14 +11,13 @@
 
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int GRID_VOLUME = 2048;                  // blocks, at most, of the two kernels that read the volume (16 bytes per thread and turn)
 constexpr int GRID_LIST = 256;                     // blocks, at most, of the kernels over slots, darts and segment heads
-
-#define SG_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 typedef unsigned long long u64;
 
@@ -147,17 +146,5 @@ __device__ __forceinline__ uint32_t gather_word(const uint8_t* __restrict__ vol,
 }
 
 inline int grid_for(u64 items, int cap) { return (int)std::max<u64>(1, std::min<u64>((u64)cap, (items + TPB - 1) / TPB)); }
-
-template <class T> int dev_alloc(T** p, size_t count, const char* what) {
-    if (hipMalloc(p, std::max<size_t>(1, count) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; vmask::set_error(std::string("out of device memory (") + what + ")"); return VRG_E_MEM; }
-    return VRG_OK;
-}
-#define SG_ALLOC(p, count, what) do { int rc_ = dev_alloc(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-inline int put(int64_t* dst, const int64_t* src, size_t count) {       // host values to a host or device array
-    if (vmask::is_device_pointer(dst)) SG_TRY(hipMemcpy(dst, src, count * sizeof(int64_t), hipMemcpyHostToDevice));
-    else std::copy(src, src + count, dst);
-    return VRG_OK;
-}
 
 }  // namespace

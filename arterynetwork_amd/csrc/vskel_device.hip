@@ -29,13 +29,12 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int WPB = TPB / 64;                      // waves per block
-
-#define VS_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 struct Geo {
     int32_t n0, n1, n2;
@@ -187,28 +186,22 @@ __global__ void __launch_bounds__(TPB) k_skel_step(uint8_t* __restrict__ P, Geo 
 
 int grid_items(uint64_t items) { return (int)std::max<uint64_t>(1, std::min<uint64_t>(16384, (items + WPB - 1) / WPB)); }
 
-struct Work { uint8_t* P = nullptr; uint32_t* list = nullptr; unsigned int* ctr = nullptr; void* in = nullptr; uint8_t* out = nullptr;
-              ~Work() { (void)hipFree(P); (void)hipFree(list); (void)hipFree(ctr); (void)hipFree(in); (void)hipFree(out); } };
-
 int skeleton(const uint8_t* volume, Geo g, uint8_t* out, int64_t* kept, int64_t* cycles) {
     const size_t V = (size_t)g.n0 * g.n1 * g.n2;
-    Work w;
-    const uint8_t* din = volume;
-    if (!vmask::is_device_pointer(volume)) {
-        VS_TRY(hipMalloc(&w.in, V));
-        VS_TRY(hipMemcpy(w.in, volume, V, hipMemcpyHostToDevice));
-        din = (const uint8_t*)w.in;
-    }
-    uint8_t* dout = out;
-    if (!vmask::is_device_pointer(out)) { VS_TRY(hipMalloc(&w.out, V)); dout = w.out; }
-    if (hipMalloc(&w.P, g.bytes()) != hipSuccess) { (void)hipGetLastError(); vmask::set_error("out of device memory (padded volume)"); return VRG_E_MEM; }
-    VS_TRY(hipMalloc(&w.ctr, C_N * sizeof(unsigned int)));
-    VS_TRY(hipMemsetAsync(w.P, 0, g.bytes(), 0));
-    VS_TRY(hipMemsetAsync(w.ctr, 0, C_N * sizeof(unsigned int), 0));
+    DevMem mem;
+    const uint8_t* din = nullptr;
+    Out<uint8_t> o;
+    int rc;
+    if ((rc = bring(mem, volume, V, "volume", &din)) || (rc = o.open(mem, out, V, "skeleton"))) return rc;
+    uint8_t* P = nullptr; uint32_t* list = nullptr; unsigned int* ctr = nullptr;
+    VMASK_GRAB(P, g.bytes(), "padded volume");
+    VMASK_GRAB(ctr, C_N, "counters");
+    VMASK_TRY(hipMemsetAsync(P, 0, g.bytes(), 0));
+    VMASK_TRY(hipMemsetAsync(ctr, 0, C_N * sizeof(unsigned int), 0));
     const int grid = grid_items(g.items());
-    k_skel_pad<<<grid, TPB>>>(din, w.P, g, w.ctr);
+    k_skel_pad<<<grid, TPB>>>(din, P, g, ctr);
     unsigned int h[8];
-    VS_TRY(hipMemcpy(h, w.ctr + C_OBJ, sizeof(h), hipMemcpyDeviceToHost));
+    VMASK_TRY(hipMemcpy(h, ctr + C_OBJ, sizeof(h), hipMemcpyDeviceToHost));
     Starts st; uint64_t nobj = 0; int sgrid[8];
     for (int s = 0; s < 8; s++) {
         st.at[s] = (uint32_t)nobj; nobj += h[C_OBJ + s];                 // (a list never holds more than its subfield's object voxels)
@@ -216,22 +209,22 @@ int skeleton(const uint8_t* volume, Geo g, uint8_t* out, int64_t* kept, int64_t*
     }
     int64_t ncycles = 0; uint64_t left = nobj;
     if (nobj) {
-        if (hipMalloc(&w.list, nobj * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); vmask::set_error("out of device memory (border lists)"); return VRG_E_MEM; }
+        VMASK_GRAB(list, nobj, "border lists");
         for (;;) {
-            VS_TRY(hipMemsetAsync(w.ctr + C_DEL, 0, (C_N - C_DEL) * sizeof(unsigned int), 0));
-            k_skel_mark<<<grid, TPB>>>(w.P, g, st, w.list, w.ctr);
-            for (int s = 0; s < 8; s++) k_skel_step<<<sgrid[s], TPB>>>(w.P, g, w.list + st.at[s], w.ctr, s);
+            VMASK_TRY(hipMemsetAsync(ctr + C_DEL, 0, (C_N - C_DEL) * sizeof(unsigned int), 0));
+            k_skel_mark<<<grid, TPB>>>(P, g, st, list, ctr);
+            for (int s = 0; s < 8; s++) k_skel_step<<<sgrid[s], TPB>>>(P, g, list + st.at[s], ctr, s);
             unsigned int deleted = 0;
-            VS_TRY(hipMemcpy(&deleted, w.ctr + C_DEL, sizeof(deleted), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&deleted, ctr + C_DEL, sizeof(deleted), hipMemcpyDeviceToHost));
             ncycles++;
             left -= deleted;
             if (!deleted) break;
         }
     } else ncycles = 1;                                                  // (the one cycle of an empty volume deletes nothing)
-    k_skel_unpad<<<grid, TPB>>>(w.P, dout, g);
-    VS_TRY(hipGetLastError());
-    if (w.out) VS_TRY(hipMemcpy(out, dout, V, hipMemcpyDeviceToHost));
-    else VS_TRY(hipDeviceSynchronize());
+    k_skel_unpad<<<grid, TPB>>>(P, o.dev, g);
+    VMASK_TRY(hipGetLastError());
+    if (o.dev == out) VMASK_TRY(hipDeviceSynchronize());
+    else if ((rc = o.close())) return rc;
     if (kept) *kept = (int64_t)left;
     if (cycles) *cycles = ncycles;
     return VRG_OK;

@@ -32,6 +32,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
@@ -43,8 +44,6 @@ constexpr int RING = 16, CHUNK = 8, AHEAD = 8, ENV_TPB = 64;
 constexpr uint32_t NO_COORD = 0xffffu;             // in the 16-bit coordinate volumes: no site on the line
 constexpr uint32_t NO_LABEL = 0xffffffffu;         // in the site-label volume: touched by no segment entry
 constexpr int CTR_PAD = 32;                        // the bad-entry counter keeps 256 bytes to itself, the sizes follow
-
-#define VT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 typedef unsigned long long u64;
 
@@ -247,75 +246,50 @@ __global__ void __launch_bounds__(ENV_TPB) k_ter_envelope(const Env a) {
 
 int grid_for(u64 items, u64 cap) { return (int)std::max<u64>(1, std::min<u64>(cap, items)); }
 
-struct Work {
-    uint8_t* mask = nullptr; uint8_t* skel = nullptr; int64_t* off = nullptr; int64_t* vox = nullptr;
-    uint32_t* SL = nullptr; u64* ctr = nullptr; uint16_t* F2 = nullptr; uint16_t* J1 = nullptr; int32_t* D1 = nullptr; uint2* SP = nullptr;
-    int32_t* labels = nullptr; int64_t* nearest = nullptr;
-    ~Work() {
-        for (void* p : {(void*)mask, (void*)skel, (void*)off, (void*)vox, (void*)SL, (void*)ctr, (void*)F2, (void*)J1, (void*)D1, (void*)SP,
-                        (void*)labels, (void*)nearest}) (void)hipFree(p);
-    }
-};
-
-template <class T> int dev_alloc(T** p, size_t count, const char* what) {
-    if (hipMalloc(p, std::max<size_t>(1, count) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; vmask::set_error(std::string("out of device memory (") + what + ")"); return VRG_E_MEM; }
-    return VRG_OK;
-}
-#define VT_ALLOC(p, count, what) do { int rc_ = dev_alloc(&(p), (count), (what)); if (rc_) return rc_; } while (0)
-
-// a device-resident copy of a host array (or the pointer itself if it already is one)
-template <class T> int stage(const T* src, size_t count, T** own, const T** d, const char* what) {
-    if (vmask::is_device_pointer(src)) { *d = src; return VRG_OK; }
-    VT_ALLOC(*own, count, what);
-    VT_TRY(hipMemcpy(*own, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *d = *own;
-    return VRG_OK;
-}
-
 int territories(const uint8_t* mask, const uint8_t* skeleton, Dim d, const int64_t* offsets, int64_t nseg, const int64_t* voxels,
                 int32_t* labels, int64_t* nearest, int64_t* sizes) {
     const u64 V = (u64)d.n0 * d.n1 * d.n2;
-    Work w;
+    DevMem mem;
     int64_t ends[2] = {0, 0};                                           // offsets[0], offsets[nseg]
     if (offsets) {
         if (vmask::is_device_pointer(offsets)) {
-            VT_TRY(hipMemcpy(&ends[0], offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
-            VT_TRY(hipMemcpy(&ends[1], offsets + nseg, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&ends[0], offsets, sizeof(int64_t), hipMemcpyDeviceToHost));
+            VMASK_TRY(hipMemcpy(&ends[1], offsets + nseg, sizeof(int64_t), hipMemcpyDeviceToHost));
         } else { ends[0] = offsets[0]; ends[1] = offsets[nseg]; }
     }
     if (ends[0] != 0 || ends[1] < 0 || (ends[1] > 0 && !voxels)) { vmask::set_error("offsets do not start at 0, or end below it, or there are no voxels"); return VRG_E_ARG; }
     const u64 total = (u64)ends[1];
     const uint8_t* dmask; const uint8_t* dskel; const int64_t* doff = nullptr; const int64_t* dvox = nullptr;
-    int rc = stage(mask, V, &w.mask, &dmask, "mask");
-    if (!rc) rc = stage(skeleton, V, &w.skel, &dskel, "skeleton");
-    if (!rc && nseg) rc = stage(offsets, (size_t)nseg + 1, &w.off, &doff, "offsets");
-    if (!rc && total) rc = stage(voxels, (size_t)total, &w.vox, &dvox, "segment voxels");
+    int rc = bring(mem, mask, V, "mask", &dmask);
+    if (!rc) rc = bring(mem, skeleton, V, "skeleton", &dskel);
+    if (!rc && nseg) rc = bring(mem, offsets, (size_t)nseg + 1, "offsets", &doff);
+    if (!rc && total) rc = bring(mem, voxels, (size_t)total, "segment voxels", &dvox);
     if (rc) return rc;
-    VT_ALLOC(w.SL, V, "site labels");
-    VT_ALLOC(w.ctr, (size_t)CTR_PAD + (size_t)nseg + 1, "sizes");
-    VT_TRY(hipMemsetAsync(w.SL, 0xff, V * sizeof(uint32_t), 0));
-    VT_TRY(hipMemsetAsync(w.ctr, 0, ((size_t)CTR_PAD + (size_t)nseg + 1) * sizeof(u64), 0));
+    uint32_t* SL = nullptr; u64* ctr = nullptr; uint16_t* F2 = nullptr; uint16_t* J1 = nullptr; int32_t* D1 = nullptr; uint2* SP = nullptr;
+    VMASK_GRAB(SL, V, "site labels");
+    VMASK_GRAB(ctr, (size_t)CTR_PAD + (size_t)nseg + 1, "sizes");
+    VMASK_TRY(hipMemsetAsync(SL, 0xff, V * sizeof(uint32_t), 0));
+    VMASK_TRY(hipMemsetAsync(ctr, 0, ((size_t)CTR_PAD + (size_t)nseg + 1) * sizeof(u64), 0));
     if (nseg) {
-        k_ter_sites<<<grid_for((std::max<u64>(total, (u64)nseg) + TPB - 1) / TPB, GRID_LIST), TPB>>>(doff, nseg, dvox, total, dskel, V, w.SL, w.ctr);
+        k_ter_sites<<<grid_for((std::max<u64>(total, (u64)nseg) + TPB - 1) / TPB, GRID_LIST), TPB>>>(doff, nseg, dvox, total, dskel, V, SL, ctr);
         u64 bad = 0;
-        VT_TRY(hipMemcpy(&bad, w.ctr, sizeof(u64), hipMemcpyDeviceToHost));
+        VMASK_TRY(hipMemcpy(&bad, ctr, sizeof(u64), hipMemcpyDeviceToHost));
         if (bad) { vmask::set_error(std::to_string(bad) + " segment entries that are no skeleton voxel of the volume (or offsets that descend)"); return VRG_E_ARG; }
     }
     const size_t lines = std::max((size_t)d.n0 * d.n2 * padded((size_t)d.n1), (size_t)d.n1 * d.n2 * padded((size_t)d.n0));
-    VT_ALLOC(w.F2, V, "row coordinates"); VT_ALLOC(w.J1, V, "plane coordinates"); VT_ALLOC(w.D1, V, "plane distances");
-    VT_ALLOC(w.SP, lines, "envelope spill area");
-    int32_t* dlab = labels; int64_t* dnear = nearest;
-    if (!vmask::is_device_pointer(labels)) { VT_ALLOC(w.labels, V, "labels"); dlab = w.labels; }
-    if (nearest && !vmask::is_device_pointer(nearest)) { VT_ALLOC(w.nearest, V, "nearest"); dnear = w.nearest; }
-    u64* cnt = w.ctr + CTR_PAD;
+    VMASK_GRAB(F2, V, "row coordinates"); VMASK_GRAB(J1, V, "plane coordinates"); VMASK_GRAB(D1, V, "plane distances");
+    VMASK_GRAB(SP, lines, "envelope spill area");
+    Out<int32_t> olab; Out<int64_t> onear;                              // (nearest is optional: never opened, its dev stays null)
+    if ((rc = olab.open(mem, labels, V, "labels")) || (nearest && (rc = onear.open(mem, nearest, V, "nearest")))) return rc;
+    u64* cnt = ctr + CTR_PAD;
 
     const uint32_t nrows = (uint32_t)d.n0 * (uint32_t)d.n1;
-    k_ter_rows<<<grid_for(((u64)nrows + ROW_WAVES - 1) / ROW_WAVES, 65535u * 16u), TPB>>>(dskel, w.F2, nrows, d.n2);
+    k_ter_rows<<<grid_for(((u64)nrows + ROW_WAVES - 1) / ROW_WAVES, 65535u * 16u), TPB>>>(dskel, F2, nrows, d.n2);
     // (every squared distance, and so every square and sum of the envelope passes, below 2^29: 32-bit arithmetic)
     const bool small = (int64_t)d.n0 * d.n0 + (int64_t)d.n1 * d.n1 + (int64_t)d.n2 * d.n2 < ((int64_t)1 << 29);
     Env e;
-    e.n1 = d.n1; e.n2 = d.n2; e.F2 = w.F2; e.J1 = w.J1; e.D1 = w.D1; e.SP = w.SP;
-    e.mask = dmask; e.SL = w.SL; e.labels = dlab; e.nearest = dnear; e.cnt = cnt; e.nlab = (uint32_t)nseg + 1u;
+    e.n1 = d.n1; e.n2 = d.n2; e.F2 = F2; e.J1 = J1; e.D1 = D1; e.SP = SP;
+    e.mask = dmask; e.SL = SL; e.labels = olab.dev; e.nearest = onear.dev; e.cnt = cnt; e.nlab = (uint32_t)nseg + 1u;
     auto egrid = [](const Env& x) { return grid_for((u64)x.nouter * ((x.ninner + 63u) / 64u), 65535u * 16u); };
     e.nouter = (uint32_t)d.n0; e.ninner = (uint32_t)d.n2; e.outer = (uint32_t)d.n1 * (uint32_t)d.n2; e.stride = (uint32_t)d.n2; e.m = d.n1;
     if (small) k_ter_envelope<int32_t, 1><<<egrid(e), ENV_TPB>>>(e);
@@ -323,11 +297,10 @@ int territories(const uint8_t* mask, const uint8_t* skeleton, Dim d, const int64
     e.nouter = 1u; e.ninner = (uint32_t)d.n1 * (uint32_t)d.n2; e.outer = 0u; e.stride = e.ninner; e.m = d.n0;
     if (small) k_ter_envelope<int32_t, 0><<<egrid(e), ENV_TPB>>>(e);
     else k_ter_envelope<long long, 0><<<egrid(e), ENV_TPB>>>(e);
-    VT_TRY(hipGetLastError());
-    VT_TRY(hipDeviceSynchronize());
-    if (w.labels) VT_TRY(hipMemcpy(labels, dlab, V * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (w.nearest) VT_TRY(hipMemcpy(nearest, dnear, V * sizeof(int64_t), hipMemcpyDeviceToHost));
-    VT_TRY(hipMemcpy(sizes, cnt, ((size_t)nseg + 1) * sizeof(int64_t), vmask::is_device_pointer(sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
+    if ((rc = olab.close()) || (rc = onear.close())) return rc;
+    VMASK_TRY(hipMemcpy(sizes, cnt, ((size_t)nseg + 1) * sizeof(int64_t), vmask::is_device_pointer(sizes) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 

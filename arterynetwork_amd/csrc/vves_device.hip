@@ -27,6 +27,7 @@
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
 #include "vmask_common.h"
+#include "vmask_host.h"
 
 namespace {
 
@@ -35,8 +36,6 @@ constexpr int TAPS = 2 * MAXR + 1;                 // pitch of one tap array; [a
 constexpr int ROW_T = 256, ROW_SEG = 128;          // k_ves_axis2: 4 waves, one row segment of 128 voxels each
 constexpr int COL_T = 1024;                        // the column passes: 16 waves
 constexpr size_t LDS_MAX = 152 * 1024;             // of the 160 KiB of a CU
-
-#define VV_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { vmask::set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return VRG_E_INTERNAL; } } while (0)
 
 // ---------------------------------------------------------------- axis 2
 template <class T>
@@ -341,48 +340,34 @@ dim3 grid_xy(int64_t n, unsigned z) {
     return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx), z);
 }
 
-struct Work {
-    void* p[16] = {};
-    int n = 0;
-    bool oom = false;
-    template <class T> T* get(size_t bytes) {
-        void* q = nullptr;
-        if (oom || n >= 16) { oom = true; return nullptr; }
-        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); oom = true; return nullptr; }
-        p[n++] = q;
-        return (T*)q;
-    }
-    ~Work() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-
 template <class T>
 int vesselness(const T* volume, int64_t n0, int64_t n1, int64_t n2, const uint8_t* mask, const std::vector<double>& taps, const int (*radii)[3],
                const double* sigmas, int nsig, const double* h, double alpha, double beta, double gamma, int bright,
                double* out, uint8_t* scale, double* gammas_used) {
     const size_t V = (size_t)n0 * n1 * n2;
-    Work w;
-    const T* din = volume; const uint8_t* dmask = mask; double* dout = out; uint8_t* dscale = scale;
+    DevMem mem;
     const bool in_host = !vmask::is_device_pointer(volume), mask_host = mask && !vmask::is_device_pointer(mask);
     const bool out_host = !vmask::is_device_pointer(out), scale_host = scale && !vmask::is_device_pointer(scale);
-    if (in_host) din = w.get<T>(V * sizeof(T));
-    if (mask_host) dmask = w.get<uint8_t>(V);
-    if (out_host) dout = w.get<double>(V * 8);
-    if (scale_host) dscale = w.get<uint8_t>(V);
-    double* G[3]; double* A[6];
-    for (auto& q : G) q = w.get<double>(V * 8);
-    for (auto& q : A) q = w.get<double>(V * 8);
-    double* dtaps = w.get<double>(taps.size() * 8);
-    unsigned long long* dmax = w.get<unsigned long long>((size_t)nsig * 8);
-    if (w.oom) { vmask::set_error("out of device memory (vesselness: the input, the output and nine float64 volumes; volumes are not processed in slabs)"); return VRG_E_MEM; }
-    if (in_host) VV_TRY(hipMemcpy((void*)din, volume, V * sizeof(T), hipMemcpyHostToDevice));
-    if (mask_host) VV_TRY(hipMemcpy((void*)dmask, mask, V, hipMemcpyHostToDevice));
-    VV_TRY(hipMemcpy(dtaps, taps.data(), taps.size() * 8, hipMemcpyHostToDevice));
-    VV_TRY(hipMemsetAsync(dmax, 0, (size_t)nsig * 8, 0));
-    VV_TRY(hipMemsetAsync(dout, 0, V * 8, 0));
-    if (dscale) VV_TRY(hipMemsetAsync(dscale, 0, V, 0));
-    VV_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-    VV_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis0<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-    VV_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis0<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+    T* own_in = nullptr; uint8_t* own_mask = nullptr; double* own_out = nullptr; uint8_t* own_scale = nullptr;
+    double* G[3] = {}; double* A[6] = {};
+    double* dtaps = nullptr; unsigned long long* dmax = nullptr;
+    bool oom = (in_host && mem.grab(&own_in, V, "input")) || (mask_host && mem.grab(&own_mask, V, "mask")) ||
+               (out_host && mem.grab(&own_out, V, "output")) || (scale_host && mem.grab(&own_scale, V, "scale"));
+    for (auto& q : G) oom = oom || mem.grab(&q, V, "derivatives");
+    for (auto& q : A) oom = oom || mem.grab(&q, V, "derivatives");
+    oom = oom || mem.grab(&dtaps, taps.size(), "taps") || mem.grab(&dmax, (size_t)nsig, "maxima");
+    if (oom) { vmask::set_error("out of device memory (vesselness: the input, the output and nine float64 volumes; volumes are not processed in slabs)"); return VRG_E_MEM; }
+    const T* din = in_host ? own_in : volume; const uint8_t* dmask = mask_host ? own_mask : mask;
+    double* dout = out_host ? own_out : out; uint8_t* dscale = scale_host ? own_scale : scale;
+    if (in_host) VMASK_TRY(hipMemcpy(own_in, volume, V * sizeof(T), hipMemcpyHostToDevice));
+    if (mask_host) VMASK_TRY(hipMemcpy(own_mask, mask, V, hipMemcpyHostToDevice));
+    VMASK_TRY(hipMemcpy(dtaps, taps.data(), taps.size() * 8, hipMemcpyHostToDevice));
+    VMASK_TRY(hipMemsetAsync(dmax, 0, (size_t)nsig * 8, 0));
+    VMASK_TRY(hipMemsetAsync(dout, 0, V * 8, 0));
+    if (dscale) VMASK_TRY(hipMemsetAsync(dscale, 0, V, 0));
+    VMASK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+    VMASK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis0<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+    VMASK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ves_axis0<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
 
     const int64_t rows = n0 * n1;
     const int vec = (n2 % 2 == 0) && ((reinterpret_cast<uintptr_t>(G[0]) | reinterpret_cast<uintptr_t>(G[1]) | reinterpret_cast<uintptr_t>(G[2])) & 15u) == 0;
@@ -405,15 +390,15 @@ int vesselness(const T* volume, int64_t n0, int64_t n1, int64_t n2, const uint8_
         if (!(gamma > 0.0)) k_ves_axis0<0><<<grid_xy(g0.ntile, 1), COL_T, lds0>>>(p6, dmask, tp, g0, M, dmax + i, nullptr, nullptr);
         k_ves_axis0<1><<<grid_xy(g0.ntile, 1), COL_T, lds0>>>(p6, dmask, tp, g0, M, dmax + i, dout, dscale);
     }
-    VV_TRY(hipGetLastError());
-    VV_TRY(hipDeviceSynchronize());
+    VMASK_TRY(hipGetLastError());
+    VMASK_TRY(hipDeviceSynchronize());
     if (gammas_used) {
         std::vector<double> m2(nsig);
-        VV_TRY(hipMemcpy(m2.data(), dmax, (size_t)nsig * 8, hipMemcpyDeviceToHost));   // (the bits of float64 values)
+        VMASK_TRY(hipMemcpy(m2.data(), dmax, (size_t)nsig * 8, hipMemcpyDeviceToHost));   // (the bits of float64 values)
         for (int i = 0; i < nsig; i++) gammas_used[i] = gamma > 0.0 ? gamma : 0.5 * std::sqrt(m2[i]);
     }
-    if (out_host) VV_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
-    if (scale_host) VV_TRY(hipMemcpy(scale, dscale, V, hipMemcpyDeviceToHost));
+    if (out_host) VMASK_TRY(hipMemcpy(out, dout, V * 8, hipMemcpyDeviceToHost));
+    if (scale_host) VMASK_TRY(hipMemcpy(scale, dscale, V, hipMemcpyDeviceToHost));
     return VRG_OK;
 }
 

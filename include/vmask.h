@@ -86,7 +86,9 @@
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
- * Return 0 on success, negative VRG_E_* codes of vrg.h otherwise.
+ * Return 0 on success, negative VRG_E_* codes of vrg.h otherwise.  A device allocation that fails is VRG_E_MEM in every call,
+ * vmask_edt, vmask_label, vmask_vessel_mask and vmask_skeleton included (they used to report some of theirs as VRG_E_INTERNAL),
+ * with a text that begins "out of device memory"; whatever the call allocated is freed on every return.
  */
 #ifndef VMASK_H
 #define VMASK_H
