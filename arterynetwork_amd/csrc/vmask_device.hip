@@ -563,7 +563,7 @@ template <class T> int deliver(T* dst, const T* dsrc, size_t n) {
     return VRG_OK;
 }
 int check(int device, int64_t n0, int64_t n1, int64_t n2, Dims& d) {
-    if (n0 < 1 || n1 < 1 || n2 < 1 || (double)n0 * n1 * n2 >= 2147483000.0 || n0 > 32000 || n1 > 32000 || n2 > 32000) { g_err = "shape out of range"; return VRG_E_ARG; }
+    if (!vmask::shape_in_envelope(n0, n1, n2)) { g_err = "shape out of range"; return VRG_E_ARG; }
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || device < 0 || device >= cnt) { (void)hipGetLastError(); g_err = "no usable HIP device (no CPU fallback)"; return VRG_E_NOGPU; }
     VMASK_TRY(hipSetDevice(device));
@@ -610,6 +610,9 @@ template <class T> int vessel_mask_impl(DevMem& mem, const uint8_t* dbrain, cons
 namespace vmask {                                  // (vmask_common.h: for vskel_device.hip)
 void set_error(const std::string& msg) { g_err = msg; }
 bool is_device_pointer(const void* p) { return is_dev(p); }
+bool shape_in_envelope(int64_t n0, int64_t n1, int64_t n2) {
+    return !(n0 < 1 || n1 < 1 || n2 < 1 || (double)n0 * n1 * n2 >= 2147483000.0 || n0 > 32000 || n1 > 32000 || n2 > 32000);
+}
 int check_args(int device, int64_t n0, int64_t n1, int64_t n2) { Dims d; return check(device, n0, n1, n2, d); }
 }  // namespace vmask
 

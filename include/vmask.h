@@ -83,6 +83,14 @@
  *                      an np.fft restatement; the corrected volume and the field within a measured distance of the model (the
  *                      device's log and exp); bit-identical repeats.  Not claimed: agreement with ITK / Slicer (their
  *                      linear-weight histogram, shrink factor, lattice refinement and convergence measure all differ).
+ *   vmask_reg_*        the "register multiple sets of images" step that the reference's README (Usage, step 1) leaves to FSL flirt:
+ *                      what a rigid / affine registration evaluates on the device - the joint histogram of the fixed volume's bins
+ *                      and the moving volume sampled through an affine voxel map, the block-mean pyramid, the resampled volume -
+ *                      and the host-only cost of a histogram, by the definition below; DESIGN.md section 9, f16.  Claimed: equality of
+ *                      the integer counts, and bit equality of the extrema, bin images, pyramids and resampled volumes, with the
+ *                      numpy restatement tests/registration_model.py; the corratio cost bit-equal to its restatement, mi and nmi
+ *                      within a measured distance (the host's log); bit-identical repeats.  Not claimed: agreement with flirt
+ *                      (its smoothing, partial-volume weights, optimiser and matrix convention all differ).
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -503,6 +511,84 @@ int vmask_bias_log_field(int device, const double* v, const uint8_t* mask, int64
 int vmask_bias_correct(int device, const void* volume, int dtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
                        const int* m0, int levels, int iterations, double threshold, int nb, double fwhm, double noise,
                        double* corrected, double* field /* may be NULL */, double* trace /* may be NULL */, int64_t* ntrace /* may be NULL */);
+
+/* Rigid / affine registration of a moving volume to a fixed one, by a definition of our own: what one cost evaluation needs on the
+ * device - the moving volume sampled at every voxel of the fixed grid through an affine voxel map and scattered into a joint
+ * histogram -, the pyramid and the resampled result.  The search is host code (registration.py).  All arithmetic is float64, EVERY
+ * OPERATION ONE IEEE DOUBLE OPERATION IN THE WRITTEN ASSOCIATION, nothing contracted into an FMA; the only atomics are integer ones.
+ * Volumes are C-contiguous, indexed (i0, i1, i2); n are the fixed extents, m the moving ones.
+ *
+ * Voxel map.  T: 12 doubles on the host, the first three rows of the 4 x 4 matrix that takes a fixed voxel index to a moving one.
+ * With W (4 x 4) taking the moving image's world coordinates to the fixed image's and the NIfTI voxel -> world affines of the two,
+ * the caller forms T = inv(movingAffine) . inv(W) . fixedAffine; the entries below are functions of T.
+ *
+ * Sample at fixed voxel (i, j, k).  Per axis a:  p_a = ((T[a][0]*i + T[a][1]*j) + T[a][2]*k) + T[a][3]  (never accumulated along a
+ * row).  The voxel is INSIDE iff 0 <= p_a <= m_a - 1 on all three axes (false for a NaN; p = -0.0 is inside).  f_a = floor(p_a),
+ * t_a = p_a - f_a, the upper neighbour's index is min(f_a + 1, m_a - 1).  Each moving value is converted to double when read
+ * (dtype VRG_F32 or VRG_F64); interpolation runs along axis 2, then axis 1, then axis 0, each step lo + t * (hi - lo):
+ *     x[a][b] = v[a][b][0] + t_2 * (v[a][b][1] - v[a][b][0]);  y[a] = x[a][0] + t_1 * (x[a][1] - x[a][0]);  value = y[0] + t_0 * (y[1] - y[0]).
+ * A sample that is not finite counts as outside - so does every sample that touches a moving value that is not finite, also with
+ * weight 0 (0 * inf is a NaN): such a value takes the up to 8 fixed voxels around it out.
+ * Nearest (order 0): q_a = floor(p_a + 0.5); inside iff 0 <= q_a <= m_a - 1; the value at q is copied in its own type.
+ *
+ * Quantisation.  b(v) = clamp(floor((v - lo) * s), 0, B - 1), clamped as a double and then converted (a NaN lands in bin 0);
+ * 8 <= B <= 128; the caller forms s = B / (hi - lo) in double, s = 0 when hi == lo. */
+
+/* lohi[0], lohi[1] (host): the exact minimum and maximum, as doubles, of the finite voxels of a VRG_F32 or VRG_F64 volume - of
+ * those with mask != 0 where mask (uint8) is not NULL; +inf, -inf when there is none.  Per-workgroup pairs are reduced on the host:
+ * the result does not depend on any order (where -0.0 and +0.0 are both extreme, either may come back).
+ * VRG_E_ARG: a dtype other than the two; a null pointer; a shape outside the envelope of the other passes. */
+int vmask_reg_minmax(int device, const void* volume, int dtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
+                     double* lohi /* 2, host */);
+
+/* bins[v] = b((double) volume[v]) with (lo, s); 255 where mask[v] == 0 (mask not NULL) or the value is not finite.  *inside (host,
+ * may be NULL) receives the number of voxels that are not 255.  VRG_E_ARG, before anything is written: B outside 8..128; lo or s not
+ * finite, s < 0; a dtype other than VRG_F32 / VRG_F64; a null pointer; a shape outside the envelope. */
+int vmask_reg_quantise(int device, const void* volume, int dtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
+                       int B, double lo, double s, uint8_t* bins, int64_t* inside /* may be NULL */);
+
+/* The joint histogram: H[bf * B + bm] = the number of fixed voxels v with bf = fixedBins[v] < B (255 marks a voxel that does not
+ * take part; any other value >= B is treated alike) whose sample is inside, bm = b(sample) with (mlo, ms).  H: B * B unsigned
+ * 64-bit counts, overwritten.  Counts are integers: they do not depend on the order of the additions, and repeats are identical.
+ * VRG_E_ARG, before anything is written: B outside 8..128; a T, mlo or ms that is not finite; a dtype other than VRG_F32 / VRG_F64;
+ * a null pointer; a fixed or moving shape outside the envelope of the other passes.  VRG_E_MEM: the bin image and the moving
+ * volume, where they are host arrays, do not fit the device (volumes are not processed in slabs); everything allocated is freed. */
+int vmask_reg_joint_hist(int device, const uint8_t* fixedBins, int64_t n0, int64_t n1, int64_t n2, const void* moving, int dtype,
+                         int64_t m0, int64_t m1, int64_t m2, const double* T /* 12, host */, int B, double mlo, double ms, uint64_t* H /* B * B */);
+
+/* The cost of a joint histogram.  Host code only: it touches no device.  N = sum H; *cost = +inf when N == 0 or
+ * (double) N < minOverlap * (double) nmask (nmask: the fixed voxels that take part).  Sums run in row-major order.
+ *   kind 0, corratio (one minus the correlation ratio of the moving bin given the fixed bin, as flirt's default): with y = bm, per
+ *     row r the 64-bit integers n_r = sum H, S_r = sum y H, Q_r = sum y^2 H, and n, S, Q their totals;
+ *         within = sum over the rows with n_r > 0, ascending from +0.0, of ((double) Q_r - ((double) S_r * (double) S_r) / (double) n_r);
+ *         total  = (double) Q - ((double) S * (double) S) / (double) n;      cost = within / total,  0 when total <= 0.
+ *     A diagonal histogram costs exactly 0.
+ *   kind 1, mi: -((H_F + H_M) - H_FM);   kind 2, nmi: -((H_F + H_M) / H_FM), 0 when H_FM is 0.
+ *     An entropy is -(sum over the non-zero counts c, ascending from +0.0, of p * log(p)), p = (double) c / (double) N, with the
+ *     host's log; H_F over the row sums, H_M over the column sums, H_FM over the cells.
+ * VRG_E_ARG: B outside 8..128; kind outside 0..2; minOverlap outside [0, 1] (a NaN included); nmask < 0; a null pointer. */
+int vmask_reg_cost(const uint64_t* H, int B, int kind, double minOverlap, int64_t nmask, double* cost);
+
+/* One level of the pyramid.  The output extent is ceil(n / 2) per axis.  A VRG_F32 or VRG_F64 volume gives float64:
+ *     out[i0][i1][i2] = 0.125 * sum over d0, d1, d2 in {0, 1} (d2 fastest, ascending from +0.0) of (double) in[min(2 i_a + d_a, n_a - 1)];
+ * a VRG_U8 mask gives uint8: 1 iff any voxel of that block is non-zero.  The voxel -> world affine of the output is
+ * A . [[2,0,0,.5],[0,2,0,.5],[0,0,2,.5],[0,0,0,1]].  VRG_E_ARG: another dtype; a null pointer; a shape outside the envelope. */
+int vmask_reg_shrink(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, void* out);
+
+/* The moving volume on the fixed grid.  order 1: out is float64, the sample above (dtype VRG_F32 or VRG_F64); order 0: out has the
+ * moving volume's type (VRG_U8, VRG_I16, VRG_I32, VRG_F32, VRG_F64), the nearest voxel.  fill is written where the voxel is
+ * outside; with order 0 it must be a value of that type.  VRG_E_ARG, before anything is written: order not 0 or 1; a dtype that
+ * the order does not take; a fill that an integer type does not hold; a T that is not finite; a null pointer; a shape outside the
+ * envelope.  VRG_E_MEM: the moving volume and the output, where they are host arrays, do not fit the device. */
+int vmask_reg_resample(int device, const void* moving, int dtype, int64_t m0, int64_t m1, int64_t m2, const double* T /* 12, host */, int order,
+                       double fill, void* out, int64_t n0, int64_t n1, int64_t n2);
+
+/* A device array that outlives a call: registration.register keeps the volumes, the pyramid and the bin images of host arrays on
+ * the device through it, so that they cross once and not with every evaluation.  *held receives `bytes` bytes of device memory,
+ * filled from `host` where that is not NULL; vmask_reg_release frees them (NULL is allowed).  VRG_E_ARG: bytes < 1, held NULL;
+ * VRG_E_NOGPU; VRG_E_MEM. */
+int vmask_reg_hold(int device, const void* host /* may be NULL */, int64_t bytes, void** held);
+void vmask_reg_release(void* held);
 
 const char* vmask_last_error(void);
 
