@@ -22,7 +22,10 @@
 //        last workgroup, checked against the sizes the band side keeps by increments.  k_recount_pipe (fp32 storage) walks the list two
 //        trips deep; 16-bit storage stays one trip deep in k_recount_bits (two deep measured slower: profiles/depth16_ab_880.json) and, on
 //        large volumes (option dense_memo), takes the intensity sum of a 256-voxel group whose voxels are all outer from a table built
-//        once per volume (VrgBackend::gsum) instead of fetching the group
+//        once per volume (VrgBackend::gsum) instead of fetching the group.  With the rim groups' tables (dense_memo = 2: isum, icnt) the
+//        walk decides per trip of three units - no inner voxel, as many outer voxels per unit as init counted included ones (vrg_rim.h) -
+//        and a trip that passes takes all twelve sums from isum: two trips per turn of a loop that fetches entries, class words, sums
+//        and counts with vector loads a turn ahead; any other trip goes group by group (rim_groups) as before
 //     -> on several GPUs: slab all-reduce -> k_dense_fin (the same check on the totals, trace sums).
 //   Stream A does not join: it runs up to two sweeps ahead of the dense pass (two copies of the class bits).
 // Labels are updated IN PLACE: measured on MI355X, streaming I + labels read-only runs at 5.8-6.0 TB/s

@@ -241,12 +241,6 @@ __device__ __forceinline__ uint32_t rim_groups(uint32_t w, uint32_t ic01, uint32
     }
     return vrg_rim_decide(a, b, inner, ic01, ic23, ne, nouter);
 }
-// the four counts of unit u behind the ngroups sums of the table, as scalar loads
-__device__ __forceinline__ void load_icnt(const double* isum, uint32_t ngroups, uint32_t u, uint32_t& ic01, uint32_t& ic23) {
-    typedef const uint32_t __attribute__((address_space(4))) cu32;
-    const cu32* p = (cu32*)(isum + ngroups) + ((size_t)u << 1);
-    ic01 = p[0]; ic23 = p[1];
-}
 // the four group sums of unit u, as scalar loads like the list entries (written by an earlier kernel only: constant address space)
 __device__ __forceinline__ void load_gsum(const double* gsum, uint32_t u, UnitSums& o) {
     typedef const double __attribute__((address_space(4))) cf64;
@@ -265,6 +259,36 @@ template <bool NT>
 __device__ __forceinline__ uint32_t load_cls(const uint32_t* cls, uint32_t u, uint32_t lane) {
     const uint32_t* pc = cls + ((size_t)u << 6) + lane;
     return NT ? __builtin_nontemporal_load(pc) : *pc;
+}
+// The walk of dense_memo = 2 decides per TRIP, not per group, whether it needs rim_groups at all (vrg_rim.h, "the unit-level decision":
+// no inner voxel and as many outer voxels per unit as init counted included ones - the argument stands there).  A lane's counts of two
+// units share a word; six DPP steps leave the wave's sums in lane 63.
+__device__ __forceinline__ uint32_t wave_total63(uint32_t x) {
+    x = dpp_add<0x111, 0xf>(x); x = dpp_add<0x112, 0xf>(x); x = dpp_add<0x114, 0xf>(x); x = dpp_add<0x118, 0xf>(x);    // row_shr 1, 2, 4, 8
+    x = dpp_add<0x142, 0xa>(x);                                  // row_bcast 15 into rows 1 and 3
+    return dpp_add<0x143, 0xc>(x);                               // row_bcast 31 into rows 2 and 3: lane 63 holds all 64 lanes'
+}
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+    const u2v b = __builtin_bit_cast(u2v, x);
+    return __builtin_bit_cast(double, u2v{(uint32_t)__builtin_amdgcn_readlane((int)b.x, l), (uint32_t)__builtin_amdgcn_readlane((int)b.y, l)});
+}
+// What the walk holds of one trip, all of it fetched with VECTOR loads of lane-distributed addresses: they return in order and their
+// number is static, so the compiler counts its waits.  Lanes 4 q .. 4 q + 3 belong to slot q of the trip (the lanes above UNITS * 4
+// repeat the last slot).  ent: the slot's list entry (its unit).  w: the class words (all 64 lanes, per slot).  gs: lane 4 q + j
+// holds sum j of slot q's unit.  ic: lanes 4 q and 4 q + 1 hold the two words of its counts.
+template <int UNITS> struct RimStage { uint32_t ent; uint32_t w[UNITS]; double gs; uint32_t ic; };
+template <int UNITS>
+__device__ __forceinline__ uint32_t rim_entries(const uint32_t* __restrict__ ulist, uint32_t k, uint32_t last, uint32_t lane) {
+    return ulist[min(k + min(lane >> 2, (uint32_t)(UNITS - 1)), last)];       // (clamped: a slot past the list's end reads the last entry and is zeroed where it is used)
+}
+// the class words, sums and counts of the units of ent (isum, icnt: the tables of k_build_rim)
+template <int UNITS, bool NT>
+__device__ __forceinline__ void rim_request(RimStage<UNITS>& s, uint32_t ent, const uint32_t* __restrict__ cls, const double* __restrict__ isum, const uint32_t* __restrict__ icnt, uint32_t lane) {
+    s.ent = ent;
+#pragma unroll
+    for (int q = 0; q < UNITS; q++) s.w[q] = load_cls<NT>(cls, (uint32_t)__builtin_amdgcn_readlane((int)ent, 4 * q), lane);
+    s.gs = isum[((size_t)ent << 2) + (lane & 3u)];
+    s.ic = icnt[((size_t)ent << 1) + (lane & 1u)];
 }
 // the intensities of the lane's 4 x 4 voxels of unit u.  SKIP: a group of four voxels that are all excluded (class 0:
 // label 4 or padding) is not fetched - the reference's dataArray[mask] gathers (:249-250) do not touch excluded voxels
@@ -309,7 +333,11 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // joins lane 0's outer sum behind the walk: a fixed order for a given grid, like every other sum of the pass.  The units
 // the slab's faces cut are counted voxel by voxel as ever.
 // RIM (with MEMO; dense_memo = 2): gsum is the table of the sums and counts of the voxels included at init (k_build_rim), and the
-// groups that take their sum from it are those of rim_groups - the full ones among them.  The unit's counts travel with its sums.
+// groups that take their sum from it are those of rim_groups - the full ones among them.  Such a pass walks the list in a loop of
+// its own (the RIM block below): entries, class words, sums and counts come through VECTOR loads a turn of two trips ahead, one
+// count per unit decides whether a trip needs rim_groups at all (vrg_rim.h), and nearly every trip does not.  (With scalar loads and
+// a decision per group the kernel spilled 73 SGPRs and stood still four times per trip, one wait behind the other: 0.087 ms per pass
+// at 880x880x640, 0.038 now - profiles/dense_unit_ab_880.json.)
 template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false, bool RIM = false>
 __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum) {
     VRG_CHAOS_POINT(7);
@@ -320,11 +348,22 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     const uint32_t* __restrict__ ulist = c.ulist;
     const uint32_t n = c.uctl[UC_N];
     const uint32_t last = n ? n - 1u : 0u;
-    uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform: the list is read through the scalar cache, ulist_entry)
+    uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform.  The list entries come through the scalar cache, ulist_entry; a RIM pass fetches them with vector loads, rim_entries)
     // (the first trip's units travel with everything else a wave reads first)
     uint32_t uu[UNITS];
+    RimStage<UNITS> D[2];                              // (RIM: the walk's window, below)
+    uint32_t E[2], en0 = 0u, en1 = 0u;
+    const uint32_t step = nwaves * UNITS;
+    if constexpr (RIM) {
+        static_assert(!RIM || UNITS == 3, "the short way packs the counts of three units into two words");
+        if (i < n) {                                   // (a wave with nothing to walk reads nothing: an empty list has no readable entry)
+            en0 = rim_entries<UNITS>(ulist, i, last, lane); en1 = rim_entries<UNITS>(ulist, i + step, last, lane);
+            E[0] = rim_entries<UNITS>(ulist, i + 2u * step, last, lane); E[1] = rim_entries<UNITS>(ulist, i + 3u * step, last, lane);
+        }
+    } else {
 #pragma unroll
-    for (int q = 0; q < UNITS; q++) uu[q] = i < n ? ulist_entry(ulist, min(i + q, last)) : 0u;     // (an empty list has no readable entry)
+        for (int q = 0; q < UNITS; q++) uu[q] = i < n ? ulist_entry(ulist, min(i + q, last)) : 0u;     // (an empty list has no readable entry)
+    }
     if (MODE == 1) {
         for (uint32_t k = threadIdx.x; k < c.L; k += TPB) s_val[k] = (float)c.lev[k];
         __syncthreads();
@@ -343,78 +382,92 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     if (f_hi < f_lo) f_hi = f_lo;
     SweepAcc acc = {0, 0, 0.0, 0.0};
     double gacc = 0.0;
-    UnitSums gs[UNITS];
-    uint32_t ic[UNITS][2];
-    const uint32_t ngroups = (uint32_t)((((uint64_t)c.PV + 1023u) >> 10) << 2);
-    if constexpr (MEMO) {
+    [[maybe_unused]] UnitSums gs[UNITS];           // (the walk of a pass without the rim tables; a RIM pass keeps its sums in its window)
+    if constexpr (MEMO && !RIM) {
 #pragma unroll
-        for (int q = 0; q < UNITS; q++) { load_gsum(gsum, uu[q], gs[q]); if constexpr (RIM) load_icnt(gsum, ngroups, uu[q], ic[q][0], ic[q][1]); }
+        for (int q = 0; q < UNITS; q++) load_gsum(gsum, uu[q], gs[q]);
     }
     // the class words of a trip are fetched one trip ahead (the intensity loads depend on them), before this trip's
     // intensities: loads return in order, so they cost no wait of their own
-    uint32_t w[UNITS];
+    [[maybe_unused]] uint32_t w[UNITS];            // (likewise)
+    if constexpr (!RIM) {
 #pragma unroll
-    for (int q = 0; q < UNITS; q++) { uu[q] = __builtin_amdgcn_readfirstlane(uu[q]); w[q] = i < n ? load_cls<NT>(cls, uu[q], lane) : 0u; }
+        for (int q = 0; q < UNITS; q++) { uu[q] = __builtin_amdgcn_readfirstlane(uu[q]); w[q] = i < n ? load_cls<NT>(cls, uu[q], lane) : 0u; }
 #pragma unroll
-    for (int q = 0; q < UNITS; q++) { asm volatile("" : "+v"(w[q])); if (i + q >= n) w[q] = 0u; }   // settle the first trip's class words here: no waits in mid-loop
+        for (int q = 0; q < UNITS; q++) { asm volatile("" : "+v"(w[q])); if (i + q >= n) w[q] = 0u; }   // settle the first trip's class words here: no waits in mid-loop
+    }
     if constexpr (RIM) {
-        // RIM: the walk of below, everything a trip ahead of where the loop below has it.  A memoising trip issues hardly an intensity load and
-        // forms hardly a sum, so what it would wait for is what it asks for itself: the list entries (a scalar load that misses: the
-        // list is streamed) and then the class words that depend on them.  Here the entries are requested three trips ahead and the class
-        // words two, a unit's sums and counts one - and a trip waits for nothing that was requested less than a trip ago, its own few
-        // intensities excepted.
-        const uint32_t step = nwaves * UNITS;
-        uint32_t un[UNITS], wn[UNITS], u2[UNITS];
-        UnitSums gn[UNITS];
-        uint32_t icn[UNITS][2];
-#pragma unroll
-        for (int q = 0; q < UNITS; q++) { un[q] = 0u; u2[q] = 0u; wn[q] = 0u; }
-        if (i < n) {                                   // (a wave with nothing to walk reads nothing: an empty list has no readable entry)
-#pragma unroll
-            for (int q = 0; q < UNITS; q++) { un[q] = ulist_entry(ulist, min(i + step + q, last)); u2[q] = ulist_entry(ulist, min(i + 2u * step + q, last)); }
-#pragma unroll
-            for (int q = 0; q < UNITS; q++) wn[q] = load_cls<NT>(cls, un[q], lane);    // (unconditionally - a slot past the list's end reads the last unit's and is zeroed where it is used -: the number of loads in flight is static)
-        }
-        uint32_t nmemo = 0u;                       // outer voxels of the trips that went the short way (they join lane 0's count behind the walk)
+        // RIM: a memoising trip issues hardly an intensity load and forms hardly a sum, so what it would wait for is what it asks for itself:
+        // the list entries and then the class words, sums and counts that depend on them.  All of these are vector loads with clamped
+        // indices, issued unconditionally.  The wave keeps a window of two trips' class words, sums and counts (D) and the entries of the
+        // two trips behind them (E).  The short way takes TWO trips per turn of its loop: it waits for the window - requested a whole
+        // turn ago -, decides both trips (vrg_rim.h: one sum per unit, two packed words per trip added over the wave and looked at in
+        // lane 63), requests the next window from E and the entries behind it, and only then adds the 2 x 12 sums, in trip, slot and
+        // group order; a group that is empty now was empty at init and its sum is +0.0, which changes nothing (gacc is never -0.0), so
+        // these are the additions rim_groups' masks select.  The loop has one body and leaves only at its top, before it has requested
+        // anything: the compiler counts a loop's waits for the fewest loads any path through its latch leaves in flight, and a ring
+        // unrolled by its depth with a way out of every trip came out with every trip waiting for the loads of the trip before.
+        // Whatever makes no whole pair of passing trips goes ALONE, the window moved on by one trip with copies: the trip that failed and
+        // its partner, and a wave's last trip where its trips are odd in number - up to about one per wave and pass, thousands on the
+        // bench volume (some 3 % of its trips), not a few dozen.  Alone, a whole trip is tested once more by itself and, if it passes,
+        // still adds its twelve sums from the table; only a trip that fails, and the list's last trip if the list ends inside it, goes
+        // the per-group way as ever: rim_groups, load_vals, stats_bits (a few dozen trips per pass on the bench volume).
+        const double* __restrict__ isum = gsum;
+        const uint32_t ngroups = (uint32_t)((((uint64_t)c.PV + 1023u) >> 10) << 2);
+        const uint32_t* __restrict__ icnt = reinterpret_cast<const uint32_t*>(gsum + ngroups);
+        if (i < n) { rim_request<UNITS, NT>(D[0], en0, cls, isum, icnt, lane); rim_request<UNITS, NT>(D[1], en1, cls, isum, icnt, lane); }
+        uint32_t nmemo = 0u;                       // this lane's outer voxels of the trips that went the short way
+        const int32_t role01 = vrg_unit_role01(lane), role2i = vrg_unit_role2i(lane);
+        auto totals = [&](const RimStage<UNITS>& t) -> uint32_t {                          // (lane 63: 0 iff the trip takes the short way, vrg_unit_short)
+            const uint32_t share = vrg_unit_share(t.ic);
+            return wave_total63(vrg_unit_word01(t.w[0], t.w[1], share, role01)) | wave_total63(vrg_unit_word2i(t.w[0], t.w[1], t.w[2], share, role2i));
+        };
         while (i < n) {
-            uint32_t u3[UNITS], w2[UNITS], fm[UNITS], ne[UNITS], no[UNITS];
+            while (i + step + UNITS <= n) {            // (two whole trips)
+                if (__builtin_amdgcn_readlane((int)(totals(D[0]) | totals(D[1])), 63) != 0) break;
+                const double g0 = D[0].gs, g1 = D[1].gs;
+                nmemo += vrg_unit_outer(D[0].w[0]) + vrg_unit_outer(D[0].w[1]) + vrg_unit_outer(D[0].w[2]) + vrg_unit_outer(D[1].w[0]) + vrg_unit_outer(D[1].w[1]) + vrg_unit_outer(D[1].w[2]);
+                rim_request<UNITS, NT>(D[0], E[0], cls, isum, icnt, lane); rim_request<UNITS, NT>(D[1], E[1], cls, isum, icnt, lane);
+                E[0] = rim_entries<UNITS>(ulist, i + 4u * step, last, lane); E[1] = rim_entries<UNITS>(ulist, i + 5u * step, last, lane);
 #pragma unroll
-            for (int q = 0; q < UNITS; q++) {          // (scalar loads return in any order, so a wait for one is a wait for all: all of a trip's are issued here, and used a trip later)
-                u3[q] = ulist_entry(ulist, min(i + 3u * step + q, last));
-                load_gsum(gsum, un[q], gn[q]); load_icnt(gsum, ngroups, un[q], icn[q][0], icn[q][1]);
+                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(g0, k);
+#pragma unroll
+                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(g1, k);
+                i += 2u * step;
             }
+            if (i >= n) break;
+            // one trip alone: the partner of a trip that failed, the failing trip itself, or a wave's last trip.  A whole trip that passes the
+            // test still takes its twelve sums from the table - the same additions in the same order as in a pair
+            if (i + UNITS <= n && __builtin_amdgcn_readlane((int)totals(D[0]), 63) == 0) {
 #pragma unroll
-            for (int q = 0; q < UNITS; q++) w2[q] = load_cls<NT>(cls, u2[q], lane);
-            bool all = true;
-#pragma unroll
-            for (int q = 0; q < UNITS; q++) {
-                if (i + q >= n) w[q] = 0u;                                         // (uniform: slots past the list's end hold nothing)
-                fm[q] = rim_groups(w[q], ic[q][0], ic[q][1], ne[q], no[q]); all = all && fm[q] == ne[q];
-            }
-            if (all) {
-                // every group of the trip that holds an included voxel takes its sum from the table (nearly every trip does): no
-                // intensity load, no per-lane count - the outer voxels are the wave's count - and nothing to wait for
-#pragma unroll
-                for (int q = 0; q < UNITS; q++) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) gacc += ((fm[q] >> j) & 1u) ? gs[q].g[j] : 0.0;      // (+0.0 changes nothing: gacc is never -0.0)
-                    nmemo += no[q];
-                }
+                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(D[0].gs, k);
+                nmemo += vrg_unit_outer(D[0].w[0]) + vrg_unit_outer(D[0].w[1]) + vrg_unit_outer(D[0].w[2]);
             } else {
+                uint32_t wq[UNITS], fm[UNITS];
                 UnitVals<MODE> f[UNITS];
 #pragma unroll
-                for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, w[q], f[q], fm[q]);
+                for (int q = 0; q < UNITS; q++) {
+                    uint32_t ne, no;
+                    wq[q] = i + q < n ? D[0].w[q] : 0u;                                    // (uniform: slots past the list's end hold nothing)
+                    uu[q] = (uint32_t)__builtin_amdgcn_readlane((int)D[0].ent, 4 * q);
+                    fm[q] = rim_groups(wq[q], (uint32_t)__builtin_amdgcn_readlane((int)D[0].ic, 4 * q), (uint32_t)__builtin_amdgcn_readlane((int)D[0].ic, 4 * q + 1), ne, no);
+                }
 #pragma unroll
-                for (int q = 0; q < UNITS; q++) stats_bits<MODE, SKIP, true>(acc, w[q], f[q], s_val, fm[q], &gs[q], &gacc, c.L);
-            }
+                for (int q = 0; q < UNITS; q++) load_vals<MODE, NT, SKIP>(c, uu[q], lane, wq[q], f[q], fm[q]);
 #pragma unroll
-            for (int q = 0; q < UNITS; q++) {
-                gs[q] = gn[q]; ic[q][0] = icn[q][0]; ic[q][1] = icn[q][1];
-                uu[q] = un[q]; w[q] = wn[q]; un[q] = u2[q]; wn[q] = w2[q]; u2[q] = u3[q];
+                for (int q = 0; q < UNITS; q++) {
+                    UnitSums gq;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) gq.g[j] = readlane_f64(D[0].gs, 4 * q + j);
+                    stats_bits<MODE, SKIP, true>(acc, wq[q], f[q], s_val, fm[q], &gq, &gacc, c.L);
+                }
             }
+            D[0] = D[1];
+            rim_request<UNITS, NT>(D[1], E[0], cls, isum, icnt, lane);
+            E[0] = E[1]; E[1] = rim_entries<UNITS>(ulist, i + 4u * step, last, lane);
             i += step;
         }
-        if (lane == 0u) acc.nout += nmemo;
+        acc.nout += nmemo;
     }
     if constexpr (!RIM) while (i < n) {              // (a RIM instantiation has walked its list above: it holds no second walk)
         const uint32_t in = i + nwaves * UNITS;
@@ -683,6 +736,8 @@ int dense_blocks(const VrgBackend* b, const VrgCtx& c) {
     // With the rim groups' memo (dense_memo = 2) a trip is short and waits for nothing it asked for itself, and the pass is flat from 1024 to
     // 2048 workgroups (tools/sweep_recount.py 880x880x640 --storage16, 60 sweeps per point, one process: 256 -> 0.166, 512 -> 0.105, 0.106,
     // 768 -> 0.090, 1024 -> 0.085, 0.085, 1280 -> 0.090, 1536 -> 0.089, 2048 -> 0.084 ms; profiles/dense_rim_ab_880.json): four per CU again.
+    // With the walk by units (vector loads of the per-unit data, one count per unit) more waves no longer help: bench.py 880x880x640, three rounds
+    // each in turn, pass 1024 -> 0.0379-0.0380 ms, 1536 -> 0.0417-0.0421, 2048 -> 0.0439-0.0442 (profiles/dense_unit_ab_880.json): four per CU stay.
     if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (dense_memo(b, c) == 1 ? 6 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
     // fp32: whole or half multiples of the CU count only - 552 or 640 workgroups leave some CUs with a wave more than others for
     // the whole pass (880x880x160: 552 -> 0.058 ms, 384 -> 0.050; 880x880x320: 640 -> 0.103, 512 -> 0.094, 768 -> 0.091 but a

@@ -35,3 +35,46 @@ VRG_RIM_HD uint32_t vrg_rim_decide(uint32_t a, uint32_t b, uint32_t inner, uint3
     ne = some | inner;
     return m & ~inner;
 }
+
+// ---- the unit-level decision of the walk's short way (k_recount_bits, RIM) ------------------------------------------------------
+// A trip of the walk takes the short way - every group's sum from the table, no intensity load - iff every group of its units that
+// holds an included voxel passes vrg_rim_decide.  That needs no count per group.  Inclusion is monotone: a voxel never becomes
+// excluded, and the excluded bit is set by init alone, so the included set of a group only grows.  In a unit without inner voxels
+// the outer voxels are the included ones, hence group by group a superset of init's included set: n_j >= icnt_j for all four groups.
+// Equal TOTALS, sum n_j == sum icnt_j, then force n_j == icnt_j in every group - each non-empty group matches its count, and a group
+// with n_j == 0 is empty and was empty at init (its table sum is +0.0).  Conversely a unit whose groups all pass has no inner voxel
+// and equal totals.  So: one population count per lane and unit (<= 16), one sum over the wave per unit (<= 1024), one comparison.
+//
+// Two units share a 32-bit word as 16-bit fields: a field reaches at most 1024 over the 64 lanes and never carries into the other.
+// A trip holds three units; the fourth field counts the INNER voxels of all three (the inner bits of the OR of the three words: a word
+// has 16 of them, so at most 16 per lane and 1024 over the wave; 0 iff no lane holds an inner voxel in any of the three), against an
+// expected count of 0, which folds "no lane holds an inner voxel" into the same sums.
+// The counts of init enter the same sums with a minus sign: the unit's four counts are two words of two 16-bit counts, each word
+// fetched by ONE lane (lanes 4 q and 4 q + 1 for slot q of the trip), which subtracts the sum of its two counts (vrg_unit_share,
+// at most 512) from the unit's field of its own word (vrg_unit_role01 / vrg_unit_role2i: -1, -65536 or 0 by the lane).  The wave adds
+// the words of its lanes with plain 32-bit additions (six DPP steps; any order gives the same totals, the arithmetic is modulo 2^32),
+// and the total of a word is D_lo + 65536 D_hi (mod 2^32) with D = a field's outer (inner) voxels minus what init counted,
+// |D| <= 1024: it is 0 iff D_lo = D_hi = 0, for |D_lo + 65536 D_hi| < 2^32 makes it 0 as an integer, 65536 then divides D_lo, so
+// D_lo = 0 and with it D_hi.  The trip takes the short way iff both totals are 0 (vrg_unit_short).
+VRG_RIM_HD uint32_t vrg_unit_outer(uint32_t w) { return (uint32_t)__builtin_popcount(w & 0xAAAAAAAAu); }
+// units 0 and 1 of a trip: this lane's outer voxels of each, one per field
+VRG_RIM_HD uint32_t vrg_unit_pack01(uint32_t w0, uint32_t w1) { return vrg_unit_outer(w0) | (vrg_unit_outer(w1) << 16); }
+// unit 2 and the inner voxels of all three
+VRG_RIM_HD uint32_t vrg_unit_pack2i(uint32_t w0, uint32_t w1, uint32_t w2) {
+    return vrg_unit_outer(w2) | ((uint32_t)__builtin_popcount((w0 | w1 | w2) & 0x55555555u) << 16);
+}
+// d: one word of a unit's counts of init (two counts of at most 256) -> their sum
+VRG_RIM_HD uint32_t vrg_unit_share(uint32_t d) { return (d & 0xffffu) + (d >> 16); }
+// what lane `lane` multiplies its share by before adding it to its two words: lanes 0, 1 hold the counts of slot 0, lanes 4, 5 those of
+// slot 1, lanes 8, 9 those of slot 2; every other lane's share counts for nothing
+VRG_RIM_HD int32_t vrg_unit_role01(uint32_t lane) { return lane < 2u ? -1 : ((lane & ~1u) == 4u ? -65536 : 0); }
+VRG_RIM_HD int32_t vrg_unit_role2i(uint32_t lane) { return (lane & ~1u) == 8u ? -1 : 0; }
+VRG_RIM_HD uint32_t vrg_unit_mul(uint32_t share, int32_t role) {
+    const int32_t r24 = (int32_t)((uint32_t)role << 8) >> 8;               // (the role as it is, visibly 24 bits wide: one full-rate multiply-add on the device)
+    return (uint32_t)((int32_t)(share & 0x3ffu) * r24);
+}
+// a lane's two words of a trip: packed counts minus its share of init's
+VRG_RIM_HD uint32_t vrg_unit_word01(uint32_t w0, uint32_t w1, uint32_t share, int32_t role01) { return vrg_unit_pack01(w0, w1) + vrg_unit_mul(share, role01); }
+VRG_RIM_HD uint32_t vrg_unit_word2i(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t share, int32_t role2i) { return vrg_unit_pack2i(w0, w1, w2) + vrg_unit_mul(share, role2i); }
+// t01, t2i: the sums of the two words over the wave's 64 lanes
+VRG_RIM_HD bool vrg_unit_short(uint32_t t01, uint32_t t2i) { return (t01 | t2i) == 0u; }
