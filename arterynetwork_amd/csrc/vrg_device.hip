@@ -277,6 +277,13 @@ __device__ __forceinline__ double readlane_f64(double x, int l) {
 // repeat the last slot).  ent: the slot's list entry (its unit).  w: the class words (all 64 lanes, per slot).  gs: lane 4 q + j
 // holds sum j of slot q's unit.  ic: lanes 4 q and 4 q + 1 hold the two words of its counts.
 template <int UNITS> struct RimStage { uint32_t ent; uint32_t w[UNITS]; double gs; uint32_t ic; };
+// The trips of a turn of the short way: the walk's window, seven VGPRs per trip and one for the entry behind it.  Measured at 2, 3 and
+// 4 (bench.py 880x880x640, 768 workgroups, three rounds each in turn: pass 0.0335 / 0.0322-0.0326 / 0.0342-0.0343 ms; four trips take
+// all 128 VGPRs).  (-DVRG_RIM_TRIPS=n builds another width for an A/B: python -m arterynetwork_amd.build --define VRG_RIM_TRIPS=2 --out ...)
+#ifndef VRG_RIM_TRIPS
+#define VRG_RIM_TRIPS 3
+#endif
+constexpr int RIM_TRIPS = VRG_RIM_TRIPS;
 template <int UNITS>
 __device__ __forceinline__ uint32_t rim_entries(const uint32_t* __restrict__ ulist, uint32_t k, uint32_t last, uint32_t lane) {
     return ulist[min(k + min(lane >> 2, (uint32_t)(UNITS - 1)), last)];       // (clamped: a slot past the list's end reads the last entry and is zeroed where it is used)
@@ -334,10 +341,11 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // the slab's faces cut are counted voxel by voxel as ever.
 // RIM (with MEMO; dense_memo = 2): gsum is the table of the sums and counts of the voxels included at init (k_build_rim), and the
 // groups that take their sum from it are those of rim_groups - the full ones among them.  Such a pass walks the list in a loop of
-// its own (the RIM block below): entries, class words, sums and counts come through VECTOR loads a turn of two trips ahead, one
-// count per unit decides whether a trip needs rim_groups at all (vrg_rim.h), and nearly every trip does not.  (With scalar loads and
+// its own (the RIM block below): entries, class words, sums and counts come through VECTOR loads a turn of RIM_TRIPS trips ahead, one
+// count per turn decides whether its trips need rim_groups at all (vrg_rim.h), and nearly every turn does not.  (With scalar loads and
 // a decision per group the kernel spilled 73 SGPRs and stood still four times per trip, one wait behind the other: 0.087 ms per pass
-// at 880x880x640, 0.038 now - profiles/dense_unit_ab_880.json.)
+// at 880x880x640; 0.038 with one count per unit - profiles/dense_unit_ab_880.json -, 0.033 with one per turn, the sums added
+// lane-parallel and three workgroups per CU - profiles/dense_turn_ab_880.json.)
 template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false, bool RIM = false>
 __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum) {
     VRG_CHAOS_POINT(7);
@@ -351,14 +359,20 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform.  The list entries come through the scalar cache, ulist_entry; a RIM pass fetches them with vector loads, rim_entries)
     // (the first trip's units travel with everything else a wave reads first)
     uint32_t uu[UNITS];
-    RimStage<UNITS> D[2];                              // (RIM: the walk's window, below)
-    uint32_t E[2], en0 = 0u, en1 = 0u;
+    constexpr int T = RIM_TRIPS;                       // (RIM: the trips of a turn of the short way)
+    RimStage<UNITS> D[T];                              // (RIM: the walk's window, below)
+    uint32_t E[T], en[T];
     const uint32_t step = nwaves * UNITS;
     if constexpr (RIM) {
         static_assert(!RIM || UNITS == 3, "the short way packs the counts of three units into two words");
+        static_assert(T >= 2 && T * UNITS <= VRG_TURN_MAX_UNITS, "one word decides a turn of at most 63 units (vrg_rim.h)");
+#pragma unroll
+        for (int k = 0; k < T; k++) { en[k] = 0u; E[k] = 0u; }
         if (i < n) {                                   // (a wave with nothing to walk reads nothing: an empty list has no readable entry)
-            en0 = rim_entries<UNITS>(ulist, i, last, lane); en1 = rim_entries<UNITS>(ulist, i + step, last, lane);
-            E[0] = rim_entries<UNITS>(ulist, i + 2u * step, last, lane); E[1] = rim_entries<UNITS>(ulist, i + 3u * step, last, lane);
+#pragma unroll
+            for (int k = 0; k < T; k++) en[k] = rim_entries<UNITS>(ulist, i + (uint32_t)k * step, last, lane);
+#pragma unroll
+            for (int k = 0; k < T; k++) E[k] = rim_entries<UNITS>(ulist, i + (uint32_t)(T + k) * step, last, lane);
         }
     } else {
 #pragma unroll
@@ -399,48 +413,39 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
     if constexpr (RIM) {
         // RIM: a memoising trip issues hardly an intensity load and forms hardly a sum, so what it would wait for is what it asks for itself:
         // the list entries and then the class words, sums and counts that depend on them.  All of these are vector loads with clamped
-        // indices, issued unconditionally.  The wave keeps a window of two trips' class words, sums and counts (D) and the entries of the
-        // two trips behind them (E).  The short way takes TWO trips per turn of its loop: it waits for the window - requested a whole
-        // turn ago -, decides both trips (vrg_rim.h: one sum per unit, two packed words per trip added over the wave and looked at in
-        // lane 63), requests the next window from E and the entries behind it, and only then adds the 2 x 12 sums, in trip, slot and
-        // group order; a group that is empty now was empty at init and its sum is +0.0, which changes nothing (gacc is never -0.0), so
-        // these are the additions rim_groups' masks select.  The loop has one body and leaves only at its top, before it has requested
-        // anything: the compiler counts a loop's waits for the fewest loads any path through its latch leaves in flight, and a ring
-        // unrolled by its depth with a way out of every trip came out with every trip waiting for the loads of the trip before.
-        // Whatever makes no whole pair of passing trips goes ALONE, the window moved on by one trip with copies: the trip that failed and
-        // its partner, and a wave's last trip where its trips are odd in number - up to about one per wave and pass, thousands on the
-        // bench volume (some 3 % of its trips), not a few dozen.  Alone, a whole trip is tested once more by itself and, if it passes,
-        // still adds its twelve sums from the table; only a trip that fails, and the list's last trip if the list ends inside it, goes
-        // the per-group way as ever: rim_groups, load_vals, stats_bits (a few dozen trips per pass on the bench volume).
+        // indices, issued unconditionally.  The wave keeps a window of T trips' class words, sums and counts (D) and the entries of the
+        // T trips behind them (E).  The short way takes T trips per turn of its loop: it waits for the window - requested a whole
+        // turn ago -, decides the turn with ONE packed word per lane added over the wave and looked at in lane 63 (vrg_rim.h, "one count
+        // per TURN"), adds the turn's sums and requests the next window from E and the entries behind it.  The sums are added where the
+        // loads left them, one per lane and trip: lane 4 q + j holds sum j of slot q, so the turn costs T additions in every lane, in
+        // walk order, into the lane's own accumulator (lsum), and lanes 0..11 join the outer sum behind the walk - a fixed order for a
+        // given grid and list.  A group that is empty now was empty at init and its sum is +0.0, which changes nothing (no accumulator
+        // ever holds -0.0), so these are the additions rim_groups' masks select.
+        // A turn that fails stays a turn (below); only a wave's last trips, fewer than T, move the window on by one trip with copies.
+        // Alone, a whole trip is tested by itself (vrg_unit_short) and, if it passes, still adds its twelve sums from the table; only a
+        // trip that fails, and the list's last trip if the list ends inside it, goes the per-group way as ever: rim_groups, load_vals,
+        // stats_bits (a few dozen trips per pass on the bench volume).
         const double* __restrict__ isum = gsum;
         const uint32_t ngroups = (uint32_t)((((uint64_t)c.PV + 1023u) >> 10) << 2);
         const uint32_t* __restrict__ icnt = reinterpret_cast<const uint32_t*>(gsum + ngroups);
-        if (i < n) { rim_request<UNITS, NT>(D[0], en0, cls, isum, icnt, lane); rim_request<UNITS, NT>(D[1], en1, cls, isum, icnt, lane); }
+        if (i < n) {
+#pragma unroll
+            for (int k = 0; k < T; k++) rim_request<UNITS, NT>(D[k], en[k], cls, isum, icnt, lane);
+        }
         uint32_t nmemo = 0u;                       // this lane's outer voxels of the trips that went the short way
+        double lsum = 0.0;                         // lane 4 q + j: sum j of slot q of those trips, added trip by trip in walk order
         const int32_t role01 = vrg_unit_role01(lane), role2i = vrg_unit_role2i(lane);
+        const uint32_t tmask = vrg_turn_mask(lane);
         auto totals = [&](const RimStage<UNITS>& t) -> uint32_t {                          // (lane 63: 0 iff the trip takes the short way, vrg_unit_short)
             const uint32_t share = vrg_unit_share(t.ic);
             return wave_total63(vrg_unit_word01(t.w[0], t.w[1], share, role01)) | wave_total63(vrg_unit_word2i(t.w[0], t.w[1], t.w[2], share, role2i));
         };
-        while (i < n) {
-            while (i + step + UNITS <= n) {            // (two whole trips)
-                if (__builtin_amdgcn_readlane((int)(totals(D[0]) | totals(D[1])), 63) != 0) break;
-                const double g0 = D[0].gs, g1 = D[1].gs;
-                nmemo += vrg_unit_outer(D[0].w[0]) + vrg_unit_outer(D[0].w[1]) + vrg_unit_outer(D[0].w[2]) + vrg_unit_outer(D[1].w[0]) + vrg_unit_outer(D[1].w[1]) + vrg_unit_outer(D[1].w[2]);
-                rim_request<UNITS, NT>(D[0], E[0], cls, isum, icnt, lane); rim_request<UNITS, NT>(D[1], E[1], cls, isum, icnt, lane);
-                E[0] = rim_entries<UNITS>(ulist, i + 4u * step, last, lane); E[1] = rim_entries<UNITS>(ulist, i + 5u * step, last, lane);
-#pragma unroll
-                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(g0, k);
-#pragma unroll
-                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(g1, k);
-                i += 2u * step;
-            }
-            if (i >= n) break;
-            // one trip alone: the partner of a trip that failed, the failing trip itself, or a wave's last trip.  A whole trip that passes the
-            // test still takes its twelve sums from the table - the same additions in the same order as in a pair
-            if (i + UNITS <= n && __builtin_amdgcn_readlane((int)totals(D[0]), 63) == 0) {
-#pragma unroll
-                for (int k = 0; k < 4 * UNITS; k++) gacc += readlane_f64(D[0].gs, k);
+        // one trip alone, the window's first, at list position pos: a trip of a turn that failed, or one of a wave's last trips.  A whole
+        // trip that passes the test still takes its twelve sums from the table - the same addition as in a turn; only a trip that fails,
+        // and the list's last trip if the list ends inside it, goes the per-group way
+        auto alone = [&](uint32_t pos) __attribute__((always_inline)) {
+            if (pos + UNITS <= n && __builtin_amdgcn_readlane((int)totals(D[0]), 63) == 0) {
+                lsum += D[0].gs;
                 nmemo += vrg_unit_outer(D[0].w[0]) + vrg_unit_outer(D[0].w[1]) + vrg_unit_outer(D[0].w[2]);
             } else {
                 uint32_t wq[UNITS], fm[UNITS];
@@ -448,7 +453,7 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
 #pragma unroll
                 for (int q = 0; q < UNITS; q++) {
                     uint32_t ne, no;
-                    wq[q] = i + q < n ? D[0].w[q] : 0u;                                    // (uniform: slots past the list's end hold nothing)
+                    wq[q] = pos + q < n ? D[0].w[q] : 0u;                                  // (uniform: slots past the list's end hold nothing)
                     uu[q] = (uint32_t)__builtin_amdgcn_readlane((int)D[0].ent, 4 * q);
                     fm[q] = rim_groups(wq[q], (uint32_t)__builtin_amdgcn_readlane((int)D[0].ic, 4 * q), (uint32_t)__builtin_amdgcn_readlane((int)D[0].ic, 4 * q + 1), ne, no);
                 }
@@ -462,12 +467,52 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
                     stats_bits<MODE, SKIP, true>(acc, wq[q], f[q], s_val, fm[q], &gq, &gacc, c.L);
                 }
             }
-            D[0] = D[1];
-            rim_request<UNITS, NT>(D[1], E[0], cls, isum, icnt, lane);
-            E[0] = E[1]; E[1] = rim_entries<UNITS>(ulist, i + 4u * step, last, lane);
+        };
+        while (i < n) {
+            while (i + (uint32_t)(T - 1) * step + UNITS <= n) {            // (T whole trips)
+                uint32_t outer = 0u, orw = 0u, shares = 0u;
+#pragma unroll
+                for (int k = 0; k < T; k++) {
+#pragma unroll
+                    for (int q = 0; q < UNITS; q++) { outer += vrg_unit_outer(D[k].w[q]); orw |= D[k].w[q]; }
+                    shares += vrg_unit_share(D[k].ic);
+                }
+                if (vrg_turn_short((uint32_t)__builtin_amdgcn_readlane((int)wave_total63(vrg_turn_word(outer, orw, shares, tmask)), 63))) {
+                    nmemo += outer;
+#pragma unroll
+                    for (int k = 0; k < T; k++) lsum += D[k].gs;
+                } else {
+                    // a turn that fails stays a turn: its trips go alone one after the other, in walk order, each as the window's first - the
+                    // window is rotated by one trip with copies, T times, and stands as it stood -, and the next window is requested as ever.
+                    // (Leaving the loop here and moving the window on trip by trip cost a wave a memory round trip per trip: with the
+                    // region's units in a few waves those waves finished 12 us behind the others, a third of the pass.)
+#pragma nounroll
+                    for (int r = 0; r < T; r++) {
+                        alone(i + (uint32_t)r * step);
+                        const RimStage<UNITS> t0 = D[0];
+#pragma unroll
+                        for (int k = 0; k + 1 < T; k++) D[k] = D[k + 1];
+                        D[T - 1] = t0;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < T; k++) rim_request<UNITS, NT>(D[k], E[k], cls, isum, icnt, lane);
+#pragma unroll
+                for (int k = 0; k < T; k++) E[k] = rim_entries<UNITS>(ulist, i + (uint32_t)(2 * T + k) * step, last, lane);
+                i += (uint32_t)T * step;
+            }
+            if (i >= n) break;
+            alone(i);                                  // (fewer than T whole trips are left: the window moves on by one trip)
+#pragma unroll
+            for (int k = 0; k + 1 < T; k++) D[k] = D[k + 1];
+            rim_request<UNITS, NT>(D[T - 1], E[0], cls, isum, icnt, lane);
+#pragma unroll
+            for (int k = 0; k + 1 < T; k++) E[k] = E[k + 1];
+            E[T - 1] = rim_entries<UNITS>(ulist, i + (uint32_t)(2 * T) * step, last, lane);
             i += step;
         }
         acc.nout += nmemo;
+        if (lane < 4u * UNITS) acc.sout += lsum;   // (the lanes above repeat the last slot's sums)
     }
     if constexpr (!RIM) while (i < n) {              // (a RIM instantiation has walked its list above: it holds no second walk)
         const uint32_t in = i + nwaves * UNITS;
@@ -738,7 +783,15 @@ int dense_blocks(const VrgBackend* b, const VrgCtx& c) {
     // 768 -> 0.090, 1024 -> 0.085, 0.085, 1280 -> 0.090, 1536 -> 0.089, 2048 -> 0.084 ms; profiles/dense_rim_ab_880.json): four per CU again.
     // With the walk by units (vector loads of the per-unit data, one count per unit) more waves no longer help: bench.py 880x880x640, three rounds
     // each in turn, pass 1024 -> 0.0379-0.0380 ms, 1536 -> 0.0417-0.0421, 2048 -> 0.0439-0.0442 (profiles/dense_unit_ab_880.json): four per CU stay.
-    if (c.lev16) return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (dense_memo(b, c) == 1 ? 6 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
+    // With one count per turn and the sums added lane-parallel (a turn of three trips) the pass wants FEWER waves: what is left of it is a fixed
+    // part - start, the tickets of sweep_finish, which queue at one address, the last workgroup's sum over the slots - and the stream itself,
+    // and the short turn lets three workgroups per CU keep the stream fed.  bench.py 880x880x640, three rounds each in turn, pass / step:
+    // 640 -> 0.0332-0.0334 / 0.0389-0.0392 ms, 768 -> 0.0322-0.0326 / 0.0382-0.0388, 1024 -> 0.0359-0.0367 / 0.0429-0.0440; the parent's walk
+    // gained nothing below 1024 (768 -> 0.0380-0.0385 / 0.0429-0.0430, 640 -> 0.0417-0.0421 / 0.0470-0.0476); profiles/dense_turn_ab_880.json.
+    if (c.lev16) {
+        const int memo = dense_memo(b, c);
+        return (int)std::min<uint64_t>(units <= 100000 ? 2 * SWEEP_BLOCKS : (memo == 1 ? 6 * SWEEP_BLOCKS : memo == 2 ? 3 * SWEEP_BLOCKS : 4 * SWEEP_BLOCKS), std::max<uint64_t>(64, units / 48));
+    }
     // fp32: whole or half multiples of the CU count only - 552 or 640 workgroups leave some CUs with a wave more than others for
     // the whole pass (880x880x160: 552 -> 0.058 ms, 384 -> 0.050; 880x880x320: 640 -> 0.103, 512 -> 0.094, 768 -> 0.091 but a
     // slower step, 0.1035 vs 0.1003, the band chain queueing behind three waves per SIMD); one session, tools/gpu_slabsweep.sh

@@ -78,3 +78,29 @@ VRG_RIM_HD uint32_t vrg_unit_word01(uint32_t w0, uint32_t w1, uint32_t share, in
 VRG_RIM_HD uint32_t vrg_unit_word2i(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t share, int32_t role2i) { return vrg_unit_pack2i(w0, w1, w2) + vrg_unit_mul(share, role2i); }
 // t01, t2i: the sums of the two words over the wave's 64 lanes
 VRG_RIM_HD bool vrg_unit_short(uint32_t t01, uint32_t t2i) { return (t01 | t2i) == 0u; }
+
+// ---- one count per TURN of the short way (k_recount_bits, RIM: a turn is RIM_TRIPS trips) ------------------------------------------
+// The argument above does not stop at a trip: ONE word decides a turn of any number of units.  A lane's word holds two fields.  The
+// low one is the lane's outer voxels of ALL units of the turn, minus its share of init's counts: lanes 4 q and 4 q + 1 (q < 3) of
+// every trip hold that trip's count words exactly as vrg_unit_share reads them, so such a lane subtracts the sum of its shares over
+// the turn's trips (vrg_turn_mask: all ones in those six lanes, 0 elsewhere).  The high field (<< 16) is the population count of the
+// inner bits of the OR of all the turn's class words.  The wave adds the words with plain 32-bit additions and looks at the total:
+//   I, the total's inner field, is 0 iff no lane holds an inner voxel in any unit of the turn.  Then, by monotone inclusion, every
+//     unit has at least as many outer voxels as init counted included ones: D = sum over the units of (outer - icnt) is a sum of
+//     terms >= 0 and is 0 iff every unit matches its count - the per-unit condition above, for every unit of every trip.
+//   If I > 0 some trip holds an inner voxel and the turn must fail whatever D is: a unit with inner voxels can hold FEWER outer voxels
+//     than init counted, and its deficit may cancel another unit's surplus - which is why the inner count has a field of its own and
+//     cannot be added into D's.
+//   Widths: a lane's OR has 16 inner bits, so I <= 1024 over the wave; |D| <= 1024 per unit, so |D| < 65536 with at most 63 units
+//     per turn (VRG_TURN_MAX_UNITS).  The total is D + 65536 I (mod 2^32) with 0 <= 65536 I <= 2^26: if I = 0 it is D mod 2^32, 0 iff
+//     D = 0; if I >= 1 it lies in (0, 2^26 + 2^16) as an integer and is not 0.  So the total is 0 iff D = I = 0.
+// A turn passes iff every one of its trips passes vrg_unit_short (tests/test_dense_turn.py runs both on the host).
+constexpr int VRG_TURN_MAX_UNITS = 63;
+VRG_RIM_HD uint32_t vrg_turn_mask(uint32_t lane) { return (lane < 12u && (lane & 2u) == 0u) ? 0xffffffffu : 0u; }
+// outer: the lane's outer voxels of all the turn's units (the sum of vrg_unit_outer); orw: the OR of their class words; shares: the sum
+// of vrg_unit_share over the lane's count words of the turn's trips
+VRG_RIM_HD uint32_t vrg_turn_word(uint32_t outer, uint32_t orw, uint32_t shares, uint32_t mask) {
+    return outer - (shares & mask) + ((uint32_t)__builtin_popcount(orw & 0x55555555u) << 16);
+}
+// total: the sum of the words over the wave's 64 lanes
+VRG_RIM_HD bool vrg_turn_short(uint32_t total) { return total == 0u; }
