@@ -18,8 +18,9 @@
 //           chip-wide kernels do the rest; the full-stencil check variant (and a lowered "small_flips") runs the item functions as device-wide kernels.
 //   stream B, the dense pass (enqueued behind the kernel that raises its request: k_close, or the k_band after a fused sweep):
 //     k_recount_pipe / k_recount_bits : the dense kernel (every listed 1024-voxel unit, HBM-bound, read-only: 4 B intensity - or a 2-B
-//        level index - of included voxels + 2 class bits per voxel): region sizes and intensity sums (:113-116, :249-250), reduced by its
-//        last workgroup, checked against the sizes the band side keeps by increments.  k_recount_pipe (fp32 storage) walks the list two
+//        level index - of included voxels + 2 class bits per voxel): region sizes and intensity sums (:113-116, :249-250), one slot per
+//        workgroup, added up in slot order by the next kernel on the stream (the next sweep's k_gate, or k_dense_close where the host looks
+//        first; option dense_close = 0 and the passes without a gate: by the pass's last workgroup), checked against the sizes the band side keeps by increments.  k_recount_pipe (fp32 storage) walks the list two
 //        trips deep; 16-bit storage stays one trip deep in k_recount_bits (two deep measured slower: profiles/depth16_ab_880.json) and, on
 //        large volumes (option dense_memo), takes the intensity sum of a 256-voxel group whose voxels are all outer from a table built
 //        once per volume (VrgBackend::gsum) instead of fetching the group.  With the rim groups' tables (dense_memo = 2: isum, icnt) the
@@ -84,6 +85,9 @@ struct VrgBackend {
     int nt_loads = -1;                                // option "nt_loads": -1 = by the size of the pass, 0 / 1 = ordinary / non-temporal loads
     int verify_every = 1;                             // option "verify_every": the dense pass on every n-th sweep only (0: never)
     int dense_pipe = 1;                               // option "dense_pipe": fp32 storage + skip_excluded run the two-trips-deep recount (k_recount_pipe)
+    int dense_close = 1;                              // option "dense_close": a gated pass is closed by the next kernel on the dense stream (0: by its own last workgroup, ticket and all)
+    bool dense_open = false; int open_fin = 2;        // ... such a pass has been enqueued with no k_dense_close behind it (dense_close_open) ...
+    VrgCtx open_c;                                    // ... and the context / kind of close that kernel is launched with
     int dense_memo = -1;                              // option "dense_memo": 16-bit storage + skip_excluded take the sums of all-outer 256-voxel groups from gsum (-1: large volumes only, 1: always, 0: never; 2: the rim groups' sums too, from isum / icnt)
     double* gsum = nullptr; size_t gsum_bytes = 0;    // sum of the values of every 256-voxel group of the padded volume (k_build_gsum), built with the level indices ...
     const uint16_t* gsum_for = nullptr;               // ... at this address (be_build_lev16); freed with them (be_free) or with the backend
@@ -252,6 +256,7 @@ __device__ void ulist_refresh(const VrgCtx& c, bool force, int p) {
 void use_device(VrgBackend* b);                                                                          // vrg_init.hip
 void init_exact(VrgBackend* b, const VrgCtx& c);                                                         // vrg_chain.hip
 void init_dense(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user);                            // vrg_device.hip
+void dense_close_open(VrgBackend* b);                                                                    // vrg_device.hip
 void build_rim(VrgBackend* b, const VrgCtx& c);                                                          // vrg_init.hip
 void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_t e_stop, be_reduce_fn cb, void* user);   // vrg_device.hip
 #pragma GCC visibility pop

@@ -1,5 +1,10 @@
 // vrg_device.hip - the dense pass of the product backend (vrg_device.h: the overview): k_gate, the recount (k_recount_pipe /
 // k_recount_bits), the class bits and the unit list, the slab close and all-reduce, and their host side - launch sizing included.
+// The dense stream runs k_gate -> pass -> k_gate -> pass ...: a pass behind a gate ends with its workgroups' slots stored (plain stores,
+// dctl[VD_OPEN] = their number) and the NEXT kernel on the stream - the kernel boundary makes the slots visible - adds them up in the fixed
+// slot order and closes the pass: the next gate, first thing and before it waits for its own request, or k_dense_close wherever the host
+// looks before another gate runs (dense_close_open: be_sync, the staged all-reduce, verify-last, the byte count, serial_streams).  The
+// passes without a gate (init, verify-last, a follower's count) and option dense_close = 0 close in the pass's last workgroup, by ticket.
 #include "vrg_device.h"
 #include "vrg_rim.h"
 
@@ -10,14 +15,16 @@ namespace {
 // ahead).  A kernel of its own (one thread), not the first thing in the recount: the recount's duration - what the HIP
 // events and rocprofv3 report for the roofline - must be streaming time only, and workgroups that wait while holding
 // LDS (the 16-bit variant: 64 KiB each) could leave no CU for k_close, which produces what they wait for.
-__device__ __forceinline__ bool gate_dense_due(const VrgCtx& c) {
-    const int64_t rseq = vrg_load_i64(&c.dctl[VD_RSEQ]);       // (only this stream changes it)
+// rseq: the recounts done (only this stream changes the word); req, stop: the caller's first look at the two gate words, fetched with
+// everything else the gate reads first - the wait looks again only while the request is really missing.
+__device__ __forceinline__ bool gate_dense_due(const VrgCtx& c, int64_t rseq, int64_t req, int64_t stop) {
     const unsigned long long t0 = wall_clock64();
     for (;;) {
-        if (vrg_load_i64(&c.gate[VG_REQ]) > rseq) return true;
-        if (vrg_load_i64(&c.gate[VG_STOP])) return vrg_load_i64(&c.gate[VG_REQ]) > rseq;   // (the last applied sweep's request is older than the stop flag)
+        if (req > rseq) return true;
+        if (stop) return vrg_load_i64(&c.gate[VG_REQ]) > rseq;   // (the last applied sweep's request is older than the stop flag)
         __builtin_amdgcn_s_sleep(4);                          // (~0.1 us per look: one thread polls, two words of one cache line)
         if (wall_clock64() - t0 > SPIN_LIMIT) { c.dctl[VD_ERR] = 10; return false; }
+        req = vrg_load_i64(&c.gate[VG_REQ]); stop = vrg_load_i64(&c.gate[VG_STOP]);
     }
 }
 
@@ -41,7 +48,57 @@ __device__ __forceinline__ void st_sc1(long long* p, long long v) { __hip_atomic
 __device__ __forceinline__ void st_sc1(double* p, double v) { __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), VRG_MO_STORE, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ long long ld_sc1(const long long* p) { return __hip_atomic_load(p, VRG_MO_LOAD, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double ld_sc1(const double* p) { return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), VRG_MO_LOAD, __HIP_MEMORY_SCOPE_AGENT)); }
-__device__ __forceinline__ void sweep_finish(const VrgCtx& c, SweepAcc a, int fin) {
+// The sum over the slots of a pass of `n` workgroups, by the first TPB threads of the calling workgroup (every thread of it calls): thread t adds
+// slots t, t + TPB, ..., then the wave butterfly, then the four wave values left to right - one fixed order whoever runs it (the pass's last
+// workgroup, the next gate, k_dense_close).  stg: the first `staged` slots as the caller has fetched them into LDS already (the gate: with
+// everything else it reads first), the four arrays one behind the other; the other slots are loaded here.  The totals are valid in thread 0.
+__device__ __forceinline__ VrgDense slots_total(const VrgCtx& c, uint32_t n, long long (*sh_n)[4], double (*sh_s)[4], uint32_t staged = 0, const long long* stg = nullptr) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long x = 0, y = 0; double sx = 0, sy = 0;
+    if (threadIdx.x < TPB) {
+        for (uint32_t i = threadIdx.x; i < n; i += TPB) {
+            if (i < staged) {
+                x += stg[i]; y += stg[staged + i];
+                sx += __builtin_bit_cast(double, stg[2 * staged + i]); sy += __builtin_bit_cast(double, stg[3 * staged + i]);
+            } else {
+                x += ld_sc1((const long long*)&c.st_nin[i]); y += ld_sc1((const long long*)&c.st_nout[i]); sx += ld_sc1(&c.st_sin[i]); sy += ld_sc1(&c.st_sout[i]);
+            }
+        }
+    }
+    x = wave_sum(x); y = wave_sum(y); sx = wave_sum(sx); sy = wave_sum(sy);
+    __syncthreads();
+    if (lane == 0 && wv < 4) { sh_n[0][wv] = x; sh_n[1][wv] = y; sh_s[0][wv] = sx; sh_s[1][wv] = sy; }
+    __syncthreads();
+    VrgDense d;
+    d.n_in = (double)(sh_n[0][0] + sh_n[0][1] + sh_n[0][2] + sh_n[0][3]);
+    d.n_out = (double)(sh_n[1][0] + sh_n[1][1] + sh_n[1][2] + sh_n[1][3]);
+    d.sum_in = ((sh_s[0][0] + sh_s[0][1]) + sh_s[0][2]) + sh_s[0][3];
+    d.sum_out = ((sh_s[1][0] + sh_s[1][1]) + sh_s[1][2]) + sh_s[1][3];
+    return d;
+}
+// ONE thread closes the recount of a sweep with this device's slab sums `d` (fin 2: one GPU, the pass is closed with it; 1: Z-slabs, the
+// staged all-reduce closes it).
+// (expect: the two sizes the pass has to reproduce, where the caller has fetched them from exp_ring already)
+__device__ __forceinline__ void recount_close(const VrgCtx& c, const VrgDense& d, int fin, const int64_t* expect = nullptr) {
+    vrg_recount_done(c, d);                          // this device's slab sums of the recount
+    if (fin == 2) vrg_dense_fin_one(c, d, expect);   // nothing to sum over ranks: close the pass here
+}
+// ... for a pass that left its slots open, by ONE thread of the next kernel on the dense stream: the same close, nothing open any more, and
+// the pass counters written through and drained - the caller may go on running (a gate waits for its own request next) while the band
+// side waits for VD_RSEQ.  (The counter tells the band side one thing only: the pass has read its class copy - it ended a kernel ago.  What
+// the close files beside it - the ring entry, the trace record - is read by later kernels of this stream and by the host behind a
+// synchronisation: plain stores.)
+__device__ __forceinline__ void close_publish(const VrgCtx& c, const VrgDense& d, int fin, const int64_t* expect = nullptr) {
+    recount_close(c, d, fin, expect);
+    c.dctl[VD_OPEN] = 0;
+    const int64_t rseq = c.dctl[VD_RSEQ], seq = c.dctl[VD_SEQ];
+    vrg_store_i64(&c.dctl[VD_RSEQ], rseq); vrg_store_i64(&c.dctl[VD_SEQ], seq);
+    vrg_drain();
+}
+// defer (option dense_close, the passes behind a gate): the workgroup leaves its slot with plain stores and the kernel ends - no drain, no
+// ticket, no closing workgroup.  The kernel boundary behind the pass makes the slots visible, and the next kernel on the dense stream sums
+// them (close_publish): the gate of the next pass, or k_dense_close where the host is about to look.  dctl[VD_OPEN] = the number of slots.
+__device__ __forceinline__ void sweep_finish(const VrgCtx& c, SweepAcc a, int fin, bool defer = false) {
     __shared__ long long sh_n[2][4];
     __shared__ double sh_s[2][4];
     __shared__ int is_last;
@@ -49,6 +106,16 @@ __device__ __forceinline__ void sweep_finish(const VrgCtx& c, SweepAcc a, int fi
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sh_n[0][wv] = a.nin; sh_n[1][wv] = a.nout; sh_s[0][wv] = a.sin_; sh_s[1][wv] = a.sout; }
     __syncthreads();
+    if (defer) {
+        if (threadIdx.x == 0) {
+            c.st_nin[blockIdx.x] = sh_n[0][0] + sh_n[0][1] + sh_n[0][2] + sh_n[0][3];
+            c.st_nout[blockIdx.x] = sh_n[1][0] + sh_n[1][1] + sh_n[1][2] + sh_n[1][3];
+            c.st_sin[blockIdx.x] = ((sh_s[0][0] + sh_s[0][1]) + sh_s[0][2]) + sh_s[0][3];
+            c.st_sout[blockIdx.x] = ((sh_s[1][0] + sh_s[1][1]) + sh_s[1][2]) + sh_s[1][3];
+            if (blockIdx.x == 0) c.dctl[VD_OPEN] = (int64_t)gridDim.x;
+        }
+        return;
+    }
     if (threadIdx.x == 0) {
         st_sc1((long long*)&c.st_nin[blockIdx.x], sh_n[0][0] + sh_n[0][1] + sh_n[0][2] + sh_n[0][3]);
         st_sc1((long long*)&c.st_nout[blockIdx.x], sh_n[1][0] + sh_n[1][1] + sh_n[1][2] + sh_n[1][3]);
@@ -62,26 +129,11 @@ __device__ __forceinline__ void sweep_finish(const VrgCtx& c, SweepAcc a, int fi
     }
     __syncthreads();
     if (!is_last) return;
-    long long x = 0, y = 0; double sx = 0, sy = 0;
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += TPB) {
-        x += ld_sc1((const long long*)&c.st_nin[i]); y += ld_sc1((const long long*)&c.st_nout[i]); sx += ld_sc1(&c.st_sin[i]); sy += ld_sc1(&c.st_sout[i]);
-    }
-    x = wave_sum(x); y = wave_sum(y); sx = wave_sum(sx); sy = wave_sum(sy);
-    __syncthreads();
-    if (lane == 0) { sh_n[0][wv] = x; sh_n[1][wv] = y; sh_s[0][wv] = sx; sh_s[1][wv] = sy; }
-    __syncthreads();
+    const VrgDense d = slots_total(c, gridDim.x, sh_n, sh_s);
     if (threadIdx.x == 0) {
-        VrgDense d;
-        d.n_in = (double)(sh_n[0][0] + sh_n[0][1] + sh_n[0][2] + sh_n[0][3]);
-        d.n_out = (double)(sh_n[1][0] + sh_n[1][1] + sh_n[1][2] + sh_n[1][3]);
-        d.sum_in = ((sh_s[0][0] + sh_s[0][1]) + sh_s[0][2]) + sh_s[0][3];
-        d.sum_out = ((sh_s[1][0] + sh_s[1][1]) + sh_s[1][2]) + sh_s[1][3];
         if (fin == 0) { *c.dn_part = d; if (c.world == 1) *c.dn = d; }   // init: the sizes found the incremental counts
         else if (fin == 4) vrg_follow_check(c, d, (uint32_t)c.fexp[0], c.fexp[1], c.fexp[2]);   // a follower's count of the sweep its apply step announced
-        else {
-            vrg_recount_done(c, d);                  // this device's slab sums of the recount
-            if (fin == 2) vrg_dense_fin_one(c, d);   // nothing to sum over ranks: close the pass here
-        }
+        else recount_close(c, d, fin);
     }
 }
 
@@ -347,14 +399,17 @@ __device__ __forceinline__ void load_vals(const VrgCtx& c, uint32_t u, uint32_t 
 // at 880x880x640; 0.038 with one count per unit - profiles/dense_unit_ab_880.json -, 0.033 with one per turn, the sums added
 // lane-parallel and three workgroups per CU - profiles/dense_turn_ab_880.json.)
 template <int UNITS, bool NT, int MODE, bool SKIP, bool MEMO = false, bool RIM = false>
-__global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum) {
+__global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, const double* gsum, int defer) {
     VRG_CHAOS_POINT(7);
-    if (check_done && check_done < 3 && !c.dctl[VD_GO]) return;     // the gate says: no sweep to count (the run has stopped) or this sweep's pass is left out
+    // (the three words a pass starts from, requested together: all written by kernels of this stream that have ended - or, for the checks
+    // that run on the band stream, behind a host synchronisation)
+    const int64_t go = c.dctl[VD_GO], rseq = c.dctl[VD_RSEQ];
+    const uint32_t n = c.uctl[UC_N];
+    if (check_done && check_done < 3 && !go) return;     // the gate says: no sweep to count (the run has stopped) or this sweep's pass is left out
     extern __shared__ __attribute__((aligned(16))) float s_val[];   // 16-bit storage: the level values (c.L floats - MODE 3: doubles -, sized at launch)
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
     const uint32_t* __restrict__ ulist = c.ulist;
-    const uint32_t n = c.uctl[UC_N];
     const uint32_t last = n ? n - 1u : 0u;
     uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform.  The list entries come through the scalar cache, ulist_entry; a RIM pass fetches them with vector loads, rim_entries)
     // (the first trip's units travel with everything else a wave reads first)
@@ -388,7 +443,7 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
         if (MEMO && threadIdx.x == 0) s_dv[c.L] = 0.0;             // (stats_group_outer_idx)
         __syncthreads();
     }
-    const uint32_t* __restrict__ cls = c.clsb[(vrg_load_i64(&c.dctl[VD_RSEQ]) + (check_done >= 3 ? 0 : 1)) & 1];   // (3: the run's last sweep, counted after all)
+    const uint32_t* __restrict__ cls = c.clsb[(rseq + (check_done >= 3 ? 0 : 1)) & 1];   // (3: the run's last sweep, counted after all)
     const uint32_t plane = (uint32_t)c.PY * (uint32_t)c.PX;
     const uint32_t lo = (2u + (uint32_t)c.z0) * plane;         // this device's Z-slab [z0, z1) as a voxel range
     const uint32_t hi = (2u + (uint32_t)c.z1) * plane;
@@ -569,7 +624,7 @@ __global__ void __launch_bounds__(TPB) k_recount_bits(VrgCtx c, int check_done, 
         load_vals<MODE, false, SKIP>(c, edge, lane, w1, f);
         stats_bits<MODE, SKIP>(acc, w1, f, s_val);
     }
-    sweep_finish(c, acc, check_done == 3 ? 0 : check_done);
+    sweep_finish(c, acc, check_done == 3 ? 0 : check_done, defer != 0);
 }
 // fp32 storage + skip_excluded (the default; option dense_pipe = 0 switches it off): the same walk, software-pipelined two
 // trips deep.  Every intensity load is issued unconditionally - a lane whose group is excluded reads one fixed dummy line
@@ -589,16 +644,17 @@ __device__ __forceinline__ void load_vals_uncond(const VrgCtx& c, uint32_t u, ui
     }
 }
 template <int UNITS, bool NT>
-__global__ void __launch_bounds__(TPB) k_recount_pipe(VrgCtx c, int check_done) {
+__global__ void __launch_bounds__(TPB) k_recount_pipe(VrgCtx c, int check_done, int defer) {
     VRG_CHAOS_POINT(8);
-    if (check_done && check_done < 3 && !c.dctl[VD_GO]) return;
+    const int64_t go = c.dctl[VD_GO], rseq = c.dctl[VD_RSEQ];      // (requested together with the list's length, as in k_recount_bits)
+    const uint32_t n = c.uctl[UC_N];
+    if (check_done && check_done < 3 && !go) return;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
     const uint32_t* __restrict__ ulist = c.ulist;
-    const uint32_t n = c.uctl[UC_N];
     const uint32_t last = n ? n - 1u : 0u, stride = nwaves * UNITS;
     uint32_t i = __builtin_amdgcn_readfirstlane(wave * UNITS);     // (wave-uniform: the list is read through the scalar cache)
-    const uint32_t* __restrict__ cls = c.clsb[(vrg_load_i64(&c.dctl[VD_RSEQ]) + (check_done >= 3 ? 0 : 1)) & 1];   // (3: the run's last sweep, counted after all)
+    const uint32_t* __restrict__ cls = c.clsb[(rseq + (check_done >= 3 ? 0 : 1)) & 1];   // (3: the run's last sweep, counted after all)
     const uint32_t plane = (uint32_t)c.PY * (uint32_t)c.PX;
     const uint32_t lo = (2u + (uint32_t)c.z0) * plane, hi = (2u + (uint32_t)c.z1) * plane;
     uint32_t f_lo = (uint32_t)(((uint64_t)lo + 1023u) >> 10), f_hi = hi >> 10;
@@ -642,7 +698,7 @@ __global__ void __launch_bounds__(TPB) k_recount_pipe(VrgCtx c, int check_done) 
         load_vals<0, false, true>(c, edge, lane, w1e, f);
         stats_bits<0, true>(acc, w1e, f, nullptr);
     }
-    sweep_finish(c, acc, check_done == 3 ? 0 : check_done);
+    sweep_finish(c, acc, check_done == 3 ? 0 : check_done, defer != 0);
 }
 
 // init: the whole unit list from the bitmap (ulist_refresh, vrg_device.h)
@@ -651,12 +707,48 @@ __global__ void __launch_bounds__(GATE_THREADS) k_ulist_init(VrgCtx c) { ulist_r
 // (or an earlier one) listed a new unit - rare: label 4 turns into 3 only next to the band
 // ... or, with option verify_every, close the sweep's pass without a count (fin = 2: one GPU, the pass is closed here; 1: the
 // marker travels through the staged all-reduce like a slab's sums).  VD_GO tells the recount behind the gate what to do.
+// Option dense_close: FIRST the gate closes the pass before it, if that one left its slots open (close_publish) - and publishes the
+// pass counters before it starts to wait, so that the band side (wait_dense_read_for) never waits for the gate's end.  Everything the gate
+// decides from is requested in one batch, ahead of any decision: the pass counters, the request and the stop word, VD_OPEN and one slot
+// per thread (a pass of up to GATE_THREADS workgroups: all of them).  What depends on those words - the sizes the open pass has to
+// reproduce, the list's generation word - is requested by thread 0 as soon as they are there and arrives while the slots are added.
+// (The generation word cannot join the first batch: the band side writes it BEFORE it raises the request, so only a load issued after
+// the request has been seen is sure to see it.)
 __global__ void __launch_bounds__(GATE_THREADS) k_gate(VrgCtx c, int every, int fin) {
     VRG_CHAOS_POINT(9);
     __shared__ int s_due, s_par;
-    if (threadIdx.x == 0) {
-        const int due = gate_dense_due(c) ? 1 : 0;
-        const int64_t seq = c.dctl[VD_RSEQ] + 1;               // the pass this gate stands in front of
+    __shared__ uint32_t s_gen;
+    __shared__ long long sh_n[2][4];
+    __shared__ double sh_s[2][4];
+    __shared__ long long s_slot[4 * GATE_THREADS];
+    const uint32_t t = threadIdx.x;
+    int64_t rseq = 0, seqc = 0, req = 0, stop = 0;
+    if (t == 0) { rseq = vrg_load_i64(&c.dctl[VD_RSEQ]); seqc = vrg_load_i64(&c.dctl[VD_SEQ]); req = vrg_load_i64(&c.gate[VG_REQ]); stop = vrg_load_i64(&c.gate[VG_STOP]); }
+    const uint32_t open = (uint32_t)vrg_load_i64(&c.dctl[VD_OPEN]);        // (uniform: only kernels of this stream write it, and they have ended)
+    {   // (nstat >= GATE_THREADS slots exist; those past the pass's grid are not added)
+        const long long x = ld_sc1((const long long*)&c.st_nin[t]), y = ld_sc1((const long long*)&c.st_nout[t]);
+        const double sx = ld_sc1(&c.st_sin[t]), sy = ld_sc1(&c.st_sout[t]);
+        s_slot[t] = x; s_slot[GATE_THREADS + t] = y;
+        s_slot[2 * GATE_THREADS + t] = __builtin_bit_cast(long long, sx); s_slot[3 * GATE_THREADS + t] = __builtin_bit_cast(long long, sy);
+    }
+    int64_t expect[2] = {0, 0};
+    uint32_t gen = 0;
+    bool early = false;
+    if (t == 0) {
+        if (open && fin == 2) { expect[0] = vrg_load_i64(&c.exp_ring[2 * ((seqc + 1) % VRG_RING)]); expect[1] = vrg_load_i64(&c.exp_ring[2 * ((seqc + 1) % VRG_RING) + 1]); }
+        const int64_t after = rseq + (open ? 1 : 0);
+        early = req > after;                                   // (the request is there already: its sweep's generation word is in place)
+        if (early) gen = vrg_load_u32(&c.uctl[UC_GEN + (int)((after + 1) & 1) * UC_GEN_STRIDE]);
+    }
+    __syncthreads();
+    if (open) {
+        const VrgDense d = slots_total(c, open, sh_n, sh_s, GATE_THREADS, s_slot);
+        if (t == 0) { close_publish(c, d, fin, fin == 2 ? expect : nullptr); rseq++; }
+    }
+    if (t == 0) {
+        const int due = gate_dense_due(c, rseq, req, stop) ? 1 : 0;
+        const int64_t seq = rseq + 1;                          // the pass this gate stands in front of
+        if (due && !early) gen = vrg_load_u32(&c.uctl[UC_GEN + (int)(seq & 1) * UC_GEN_STRIDE]);
         int go = due;
         if (due && vrg_dense_skipped(seq, every, c.ver_n, c.ver_me)) {
             vrg_recount_done(c, vrg_dense_skip_marker());
@@ -664,10 +756,20 @@ __global__ void __launch_bounds__(GATE_THREADS) k_gate(VrgCtx c, int every, int 
             go = 0;
         }
         c.dctl[VD_GO] = go;
-        s_due = due; s_par = (int)(seq & 1);
+        s_due = due; s_par = (int)(seq & 1); s_gen = gen;
     }
     __syncthreads();
-    if (s_due) ulist_refresh(c, false, s_par);                 // (also for a pass that is left out: its sweep's new units join the bitmap at THEIR gate)
+    if (s_due && s_gen) ulist_refresh(c, false, s_par);        // (also for a pass that is left out: its sweep's new units join the bitmap at THEIR gate.  It looks at the word again)
+}
+// ... and where no gate will follow before somebody looks at the pass counters, the trace or the ring (the host, the staged all-reduce,
+// a kernel of the other stream behind a host synchronisation): one workgroup that closes the pass before it, if that one is open
+__global__ void __launch_bounds__(TPB) k_dense_close(VrgCtx c, int fin) {
+    __shared__ long long sh_n[2][4];
+    __shared__ double sh_s[2][4];
+    const uint32_t open = (uint32_t)vrg_load_i64(&c.dctl[VD_OPEN]);
+    if (!open) return;                                         // (uniform)
+    const VrgDense d = slots_total(c, open, sh_n, sh_s);
+    if (threadIdx.x == 0) close_publish(c, d, fin);
 }
 __global__ void k_verify_last(VrgCtx c) { vrg_dense_verify_last(c, c.world == 1 ? *c.dn_part : *c.dn); }
 __global__ void k_cls_build(VrgCtx c) {
@@ -830,6 +932,7 @@ constexpr int DENSE_GROUP = 8;
 static_assert(DENSE_GROUP <= VRG_STAGE, "staging buffer");
 static void reduce_staged(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     b->dense_pending = 0;
+    dense_close_open(b);                             // (the last recount's slab sums join the ring first)
     k_dense_pack<<<1, 1, 0, b->sb>>>(c);
     if (b->comm) {
         ncclResult_t r = ncclAllReduce(c.stage_in, c.stage_out, 4 * VRG_STAGE, ncclDouble, ncclSum, b->comm, b->sb);
@@ -858,25 +961,25 @@ static bool dense_deep(const VrgBackend* b, const VrgCtx& c) { return b->dense_p
 // The start / stop events ride on the dispatch itself (hipExtLaunchKernel): no separate event packets in the stream,
 // which cost ~4 us each between two back-to-back recounts.
 template <bool NT, bool SKIP>
-static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep, const double* gsum, bool rim, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
+static void launch_recount_as(const VrgCtx& c, int blocks, int check, int defer, bool deep, const double* gsum, bool rim, hipStream_t st, hipEvent_t e_start, hipEvent_t e_stop) {
     const double* const none = nullptr;
     if constexpr (SKIP) {
-        if (deep) { hipExtLaunchKernelGGL((k_recount_pipe<3, NT>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check); return; }
+        if (deep) { hipExtLaunchKernelGGL((k_recount_pipe<3, NT>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, defer); return; }
         if (gsum && rim) {     // (dense_memo = 2: gsum is the table of build_rim)
-            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum);
-            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum);
+            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum, defer);
+            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum, defer);
             return;
         }
         if (gsum) {            // (dense_memo: 16-bit storage)
-            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum);
-            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum);
+            if (c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, true, true>), dim3(blocks), dim3(TPB), (c.L + 1) * sizeof(double), st, e_start, e_stop, 0, c, check, gsum, defer);
+            else hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, true, true>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, gsum, defer);
             return;
         }
     }
-    if (c.lev16 && c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(double), st, e_start, e_stop, 0, c, check, none);
-    else if (c.lev16) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, none);
-    else if (c.I) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 0, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none);
-    else hipExtLaunchKernelGGL((k_recount_bits<2, NT, 2, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none);
+    if (c.lev16 && c.L <= TAB64_LEVELS) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 3, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(double), st, e_start, e_stop, 0, c, check, none, defer);
+    else if (c.lev16) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 1, SKIP>), dim3(blocks), dim3(TPB), c.L * sizeof(float), st, e_start, e_stop, 0, c, check, none, defer);
+    else if (c.I) hipExtLaunchKernelGGL((k_recount_bits<3, NT, 0, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none, defer);
+    else hipExtLaunchKernelGGL((k_recount_bits<2, NT, 2, SKIP>), dim3(blocks), dim3(TPB), 0, st, e_start, e_stop, 0, c, check, none, defer);
 }
 // One dense pass of this handle on stream st: the gate in front of a sweep's pass (checks 1 and 2: it waits, on the device, until the
 // sweep's labels are in place, and keeps the unit list current; also when every pass is counted - with several verifiers this handle
@@ -884,14 +987,25 @@ static void launch_recount_as(const VrgCtx& c, int blocks, int check, bool deep,
 // trips deep where there is such a kernel (dense_deep: fp32 storage); the init count (0) and the verify-last count (3) run once: one trip deep.
 // Non-temporal loads (dense_nt): for a pass that is larger than the 256-MiB Infinity Cache, where nothing is worth keeping; a smaller
 // slab is read with ordinary loads and then comes out of that cache sweep after sweep.
+// Option dense_close (default 1): a pass behind a gate leaves its slots open, and the next kernel on the dense stream closes it - the next
+// gate, or k_dense_close wherever the host (or a kernel it orders behind the stream) looks first: dense_close_open.  dense_open: such a pass
+// has been enqueued and no k_dense_close behind it yet (the pass may have returned at its gate's word, or a later gate may have closed it:
+// k_dense_close then finds nothing open); open_c / open_fin: what that kernel is launched with.
 static void launch_recount(VrgBackend* b, const VrgCtx& c, int check, hipStream_t st, hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr) {
     const int blocks = dense_blocks(b, c);
     const bool nt = dense_nt(b, c), deep = dense_deep(b, c) && check != 0 && check != 3;
+    const int defer = (check == 1 || check == 2) && b->dense_close ? 1 : 0;
     if (check == 1 || check == 2) k_gate<<<1, GATE_THREADS, 0, st>>>(c, b->verify_every, check);
     const int memo = dense_memo(b, c);
     const double* const gsum = memo == 2 ? b->isum : (memo ? b->gsum : nullptr);
-    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, deep, gsum, memo == 2, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, deep, gsum, memo == 2, st, e_start, e_stop); }
-    else { if (nt) launch_recount_as<true, false>(c, blocks, check, deep, nullptr, false, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, deep, nullptr, false, st, e_start, e_stop); }
+    if (b->skip) { if (nt) launch_recount_as<true, true>(c, blocks, check, defer, deep, gsum, memo == 2, st, e_start, e_stop); else launch_recount_as<false, true>(c, blocks, check, defer, deep, gsum, memo == 2, st, e_start, e_stop); }
+    else { if (nt) launch_recount_as<true, false>(c, blocks, check, defer, deep, nullptr, false, st, e_start, e_stop); else launch_recount_as<false, false>(c, blocks, check, defer, deep, nullptr, false, st, e_start, e_stop); }
+    if (defer) { b->dense_open = true; b->open_c = c; b->open_fin = check; }
+}
+void dense_close_open(VrgBackend* b) {
+    if (!b->dense_open) return;
+    b->dense_open = false;
+    k_dense_close<<<1, TPB, 0, b->sb>>>(b->open_c, b->open_fin);
 }
 
 // init: the class bits and the unit list from the labels, then the first count (the sizes the sweeps keep by increments start from it)
@@ -910,8 +1024,8 @@ void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_
     if (b->serial) HIP_CHECK(hipStreamSynchronize(b->sa));
     const bool ranks = !b->repl && (c.world > 1 || b->comm || cb);
     launch_recount(b, c, ranks ? 1 : 2, b->sb, e_start, e_stop);
-    if (b->serial) HIP_CHECK(hipStreamSynchronize(b->sb));
-    // one GPU: the last workgroup of the recount closes the pass itself.  Z-slabs: the slab sums of DENSE_GROUP recounts
+    if (b->serial) { dense_close_open(b); HIP_CHECK(hipStreamSynchronize(b->sb)); }      // (the band kernels the host enqueues next wait for this pass's counter)
+    // one GPU: the next kernel on the stream closes the pass (option dense_close = 0: the recount's last workgroup does).  Z-slabs: the slab sums of DENSE_GROUP recounts
     // are summed over the ranks by ONE all-reduce (nothing on the band side waits for it: the decisions use the
     // incremental sizes; the totals are only cross-checked against them and filed in the trace)
     if (ranks && ++b->dense_pending >= DENSE_GROUP) reduce_staged(b, c, cb, user);
@@ -921,6 +1035,7 @@ void enqueue_dense(VrgBackend* b, const VrgCtx& c, hipEvent_t e_start, hipEvent_
 // after all and compared with the sizes kept by increments (collective on several ranks)
 void be_verify_last(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     use_device(b);
+    if (b->dense_open) { dense_close_open(b); HIP_CHECK(hipStreamSynchronize(b->sb)); }   // (the count below reads the pass counter on the band stream)
     launch_recount(b, c, 3, b->sa);      // (check 3: no gate - launch_recount puts one in front of checks 1 and 2 only)
     reduce_dense(b, c, cb, user, b->sa);
     k_verify_last<<<1, 1, 0, b->sa>>>(c);
@@ -931,6 +1046,7 @@ void be_dense_flush(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user)
     use_device(b);
     const bool ranks = !b->repl && (c.world > 1 || b->comm || cb);
     if (ranks && b->dense_pending) reduce_staged(b, c, cb, user);
+    dense_close_open(b);
 }
 
 void be_follow_count(VrgBackend* b, const VrgCtx& c, VrgEvents* ev) {
@@ -961,6 +1077,7 @@ uint64_t be_dense_bytes(VrgBackend* b, const VrgCtx& c) {
         const uint64_t bpv4 = c.lev16 ? 9 : (c.I ? 17 : 33);      // 4 x (intensity bytes + 0.25)
         return (hi - lo) * bpv4 / 4;
     }
+    dense_close_open(b);                 // (k_dense_bytes reads the pass counter: which class copy the last pass read)
     HIP_CHECK(hipStreamSynchronize(b->sb));
     unsigned long long* d = nullptr; unsigned long long v[3] = {0, 0, 0};
     HIP_CHECK(hipMalloc(&d, 24));

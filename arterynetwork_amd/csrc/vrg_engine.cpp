@@ -388,7 +388,7 @@ int API(set_option)(vrg_handle* h, const char* name, int64_t value) {
     else if (n == "bin_above") { if (value < 0) return fail(h, VRG_E_ARG, "bin_above: a number of levels >= 0"); h->bin_above = value; h->inited = false; }
     else if (n == "verify_every") { if (value < 0) return fail(h, VRG_E_ARG, "verify_every: 0 (never), 1 (every sweep: the default) or n > 1 (every n-th sweep)"); h->verify_every = (int)std::min<int64_t>(value, 1 << 20); be_set_tuning(h->be, name, value); }
     else if (n == "open_sweeps" || n == "mark_compact" || n == "band_blocks_max") be_set_tuning(h->be, name, value);
-    else if (n == "sweep_blocks" || n == "prio_mode" || n == "small_flips" || n == "fuse_max" || n == "memo_above" || n == "serial_streams" || n == "skip_excluded" || n == "nt_loads" || n == "dense_pipe" || n == "dense_memo") be_set_tuning(h->be, name, value);
+    else if (n == "sweep_blocks" || n == "prio_mode" || n == "small_flips" || n == "fuse_max" || n == "memo_above" || n == "serial_streams" || n == "skip_excluded" || n == "nt_loads" || n == "dense_pipe" || n == "dense_memo" || n == "dense_close") be_set_tuning(h->be, name, value);
     else if (n == "storage16") h->storage16 = value < 0 ? -1 : (value != 0);      // takes effect at the next vrg_init
     else if (n == "narrow_alloc_fault") h->narrow_alloc_fault = value != 0;   // tests: the 2 B/voxel buffer cannot be allocated (automatic mode keeps the stored type; storage16 = 1 fails)
     else if (n == "narrow_above") { if (value < 0) return fail(h, VRG_E_ARG, "narrow_above: a number of bytes >= 0"); h->narrow_above = value; }   // ... as does this

@@ -272,6 +272,7 @@ void be_set_tuning(VrgBackend* b, const char* name, long long v) {
     if (std::strcmp(name, "band_hint") == 0) b->band_hint = (uint32_t)std::min<long long>(std::max<long long>(v, 0), 0x7fffffff);
     if (std::strcmp(name, "direct_hint") == 0) b->direct_hint = v != 0;
     if (std::strcmp(name, "dense_pipe") == 0) b->dense_pipe = (int)v;
+    if (std::strcmp(name, "dense_close") == 0) { dense_close_open(b); b->dense_close = v != 0; }
     if (std::strcmp(name, "dense_memo") == 0) b->dense_memo = v < 0 ? -1 : (v == 2 ? 2 : (v != 0));
     if (std::strcmp(name, "memo_above") == 0 && v >= 0) b->memo_above = (uint32_t)std::min<long long>(v, 0x7fffffff);
     if (std::strcmp(name, "verify_every") == 0 && v >= 0) b->verify_every = (int)std::min<long long>(v, 1 << 20);
@@ -304,7 +305,7 @@ const char* be_last_error(VrgBackend* b) {
 void be_clear_error(VrgBackend* b) { b->err[0] = 0; }
 // (the engine synchronises when a run ends or a trip was handed back: no fused sweep is waiting for its dense pass then)
 bool be_band_busy(VrgBackend* b) { use_device(b); const hipError_t e = hipStreamQuery(b->sa); if (e == hipErrorNotReady) { (void)hipGetLastError(); return true; } return false; }
-void be_sync(VrgBackend* b) { use_device(b); HIP_CHECK(hipStreamSynchronize(b->sa)); HIP_CHECK(hipStreamSynchronize(b->sb)); if (b->sd) HIP_CHECK(hipStreamSynchronize(b->sd)); b->fused_prev = false; b->prev_open = false; }
+void be_sync(VrgBackend* b) { use_device(b); dense_close_open(b); HIP_CHECK(hipStreamSynchronize(b->sa)); HIP_CHECK(hipStreamSynchronize(b->sb)); if (b->sd) HIP_CHECK(hipStreamSynchronize(b->sd)); b->fused_prev = false; b->prev_open = false; }
 
 // A device-resident input is read on the library's own stream: the caller's producer must have finished (vrg.h).
 // ---- host arrays in and out --------------------------------------------------------------------------------------------------------
@@ -617,6 +618,7 @@ void be_init_sort(VrgBackend* b, const VrgCtx& c, uint32_t n_in, uint32_t n_out)
 void be_init_finish(VrgBackend* b, const VrgCtx& c, be_reduce_fn cb, void* user) {
     use_device(b);
     b->dense_pending = 0;
+    dense_close_open(b);
     HIP_CHECK(hipStreamSynchronize(b->sb));     // both class copies are rebuilt: no dense pass may be in flight
     k_init_entry<<<ITEM_BLOCKS, TPB, 0, b->sa>>>(c);
     if (c.I && c.L <= HIST_LDS_LEVELS) k_hist_lds<<<1024, TPB, 0, b->sa>>>(c);

@@ -932,14 +932,16 @@ VRG_HD void vrg_recount_done(const VrgCtx& c, const VrgDense& part) {
     c.dctl[VD_RSEQ] = rseq;
 }
 // close pass seq = passes closed + 1 with its totals over all slabs: cross-check the sizes it had to reproduce, file the sums
-VRG_HD void vrg_dense_fin_one(const VrgCtx& c, const VrgDense& d) {
+// (expect: the two sizes of exp_ring the pass must reproduce, where the caller holds them already)
+VRG_HD void vrg_dense_fin_one(const VrgCtx& c, const VrgDense& d, const int64_t* expect = nullptr) {
     const int64_t seq = c.dctl[VD_SEQ] + 1;
     if (d.n_in < 0.0) {                                   // a pass that was left out (verify_every): no sums for this sweep's trace record
         if ((uint64_t)seq < c.trace_cap) { c.trace[seq].sum_in = __builtin_nan(""); c.trace[seq].sum_out = __builtin_nan(""); }
         c.dctl[VD_SEQ] = seq;
         return;
     }
-    if ((int64_t)d.n_in != c.exp_ring[2 * (seq % VRG_RING)] || (int64_t)d.n_out != c.exp_ring[2 * (seq % VRG_RING) + 1]) c.dctl[VD_ERR] = 5;
+    const int64_t e_in = expect ? expect[0] : c.exp_ring[2 * (seq % VRG_RING)], e_out = expect ? expect[1] : c.exp_ring[2 * (seq % VRG_RING) + 1];
+    if ((int64_t)d.n_in != e_in || (int64_t)d.n_out != e_out) c.dctl[VD_ERR] = 5;
     if ((uint64_t)seq < c.trace_cap) { c.trace[seq].sum_in = d.sum_in; c.trace[seq].sum_out = d.sum_out; }
     *c.dn = d;
     c.dctl[VD_SEQ] = seq;
@@ -969,7 +971,7 @@ VRG_HD void vrg_dense_fin_staged(const VrgCtx& c) {
 // init: the dense pass founds the incremental sizes
 VRG_HD void vrg_init_counts(const VrgCtx& c) {
     c.inc[VC_NIN] = (int64_t)c.dn->n_in; c.inc[VC_NOUT] = (int64_t)c.dn->n_out; c.gate[VG_REQ] = 0; c.gate[VG_STOP] = 0;
-    c.dctl[VD_SEQ] = 0; c.dctl[VD_ERR] = 0; c.dctl[VD_RSEQ] = 0; c.dctl[VD_NST] = 0; c.dctl[VD_GO] = 0; c.nchg[0] = 0; c.nchg[1] = 0;
+    c.dctl[VD_SEQ] = 0; c.dctl[VD_ERR] = 0; c.dctl[VD_RSEQ] = 0; c.dctl[VD_NST] = 0; c.dctl[VD_GO] = 0; c.dctl[VD_OPEN] = 0; c.nchg[0] = 0; c.nchg[1] = 0;
 }
 
 // ------------------------------------------------------------------ the change log (leader / follower replication)

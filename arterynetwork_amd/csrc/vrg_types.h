@@ -198,7 +198,10 @@ enum { VG_REQ = 0, VG_STOP = 1 };
 // disagreed with the incremental sizes; VD_NST: entries of the staged all-reduce
 // VD_GO: written by the gate in front of a recount - 1: count the sweep now; 0: nothing to count (the run has stopped) or the
 // sweep's pass is left out (option verify_every)
-enum { VD_SEQ = 0, VD_ERR = 1, VD_RSEQ = 2, VD_NST = 3, VD_GO = 4 };
+// VD_OPEN: a gated pass that counted has left its workgroups' slots (st_*) unsummed - this many of them - for the next kernel on the
+// dense stream to close (the next gate, or k_dense_close); 0: nothing is open.  Written by the dense stream only, across kernel
+// boundaries: a pass that counts sets it, whoever closes the pass zeroes it.
+enum { VD_SEQ = 0, VD_ERR = 1, VD_RSEQ = 2, VD_NST = 3, VD_GO = 4, VD_OPEN = 5 };
 enum { UC_N = 0, UC_GEN = 16, UC_GEN_STRIDE = 16 };       // VrgCtx::uctl: list length; units newly listed by the sweeps of parity p at UC_GEN + p * UC_GEN_STRIDE (own cache lines)
 enum { VRG_RING = 64, VRG_STAGE = 16 };
 // diagnostic build (-DVRG_STAMPS): per-workgroup time stamps of one kernel behind the chain's 64 (VrgCtx::dbg): VRG_DBG_PER words for each of VRG_DBG_WG workgroups

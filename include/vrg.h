@@ -126,6 +126,10 @@ const char* vrg_last_error(const vrg_handle* h);
  *                    16-bit pass, all-outer groups only; 0: none (the kernel of before, bit for bit).  The sums of such groups are added in another order:
  *                    sum_in / sum_out are bit-identical on data whose partial sums are exact (integers, coarse
  *                    quantisations) and differ in the last bits otherwise.
+ *   "dense_close"    any time; 1 (default): a sweep's dense pass ends with its workgroups' partial sums stored, and the next
+ *                    kernel on the dense stream adds them up and files the sweep's sizes and sums - the gate in front of the next
+ *                    pass, or a one-workgroup kernel wherever the host is about to look; 0: the pass's own last workgroup
+ *                    does, behind an arrival ticket.  The additions are made in the same order: same results bit for bit.
  *   "verify_every"   any time; n = 1 (default): the dense pass over every voxel - the reference's recount of innerSize /
  *                    outerSize (:113-116), here a CHECK of the sizes the decisions read (kept by increments) and the source
  *                    of the trace's intensity sums - runs after every sweep; n > 1: after every n-th sweep; 0: never.
