@@ -26,10 +26,14 @@
 
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
+#include "vmask_cc.h"
 #include "vmask_common.h"
 #include "vmask_host.h"
 
 namespace {
+
+using vmask::CcRank;
+using vmask::cc_rank;
 
 constexpr int TPB = 256;
 constexpr int32_t EDT_INF = 1 << 29;
@@ -445,10 +449,7 @@ __global__ void __launch_bounds__(TPB) k_cc_flatten(const int32_t* __restrict__ 
 // roots before its 64-voxel word (off: an exclusive scan over the words' popcounts - V / 64 elements instead of the V-element
 // scan of a flag array, which was the slowest kernel of the labelling, 1.5 ms at 880x880x640, and 8 bytes per voxel of
 // scratch) + the roots below it inside the word.  Both arrays together are 12 bytes per 64 voxels: cache-resident.
-struct CcRank { const unsigned long long* bits; const uint32_t* off; };
-__device__ __forceinline__ uint32_t cc_rank(CcRank k, uint32_t r) {
-    return k.off[r >> 6] + (uint32_t)__popcll(k.bits[r >> 6] & ((1ull << (r & 63u)) - 1ull));
-}
+// (CcRank, cc_rank: vmask_cc.h)
 struct PopcU64 { __host__ __device__ uint32_t operator()(unsigned long long w) const { return (uint32_t)__builtin_popcountll(w); } };
 __global__ void __launch_bounds__(TPB) k_cc_sizes(const int32_t* __restrict__ root, CcRank rk, unsigned long long* __restrict__ sizes, uint32_t V) {
     const int4* __restrict__ r4 = reinterpret_cast<const int4*>(root);      // (root is this library's own array: aligned as every device allocation)
@@ -489,7 +490,8 @@ __global__ void __launch_bounds__(TPB) k_cc_filter(const int32_t* __restrict__ r
 struct CC { int32_t* parent = nullptr; int32_t* root = nullptr; unsigned long long* bits = nullptr; uint32_t* off = nullptr; unsigned long long* sizes = nullptr; uint8_t* tmp = nullptr; uint32_t ncomp = 0;
             CcRank rank() const { return CcRank{bits, off}; } };
 
-int cc_run(DevMem& mem, const uint8_t* dvol, Dims d, int connectivity, CC& c) {
+// (with_sizes false: no size table and no size pass - c.sizes stays null)
+int cc_run(DevMem& mem, const uint8_t* dvol, Dims d, int connectivity, CC& c, bool with_sizes = true) {
     uint32_t V = (uint32_t)d.n0 * d.n1 * d.n2;
     const size_t nw = ((size_t)V + 63) / 64;
     VMASK_GRAB(c.parent, V, "component parents"); VMASK_GRAB(c.root, V, "component roots"); VMASK_GRAB(c.bits, nw, "root bitmap"); VMASK_GRAB(c.off, nw, "root counts");
@@ -505,6 +507,7 @@ int cc_run(DevMem& mem, const uint8_t* dvol, Dims d, int connectivity, CC& c) {
     VMASK_TRY(hipMemcpy(&last_off, c.off + (nw - 1), 4, hipMemcpyDeviceToHost));
     VMASK_TRY(hipMemcpy(&last_bits, c.bits + (nw - 1), 8, hipMemcpyDeviceToHost));
     c.ncomp = last_off + (uint32_t)__builtin_popcountll(last_bits);
+    if (!with_sizes) { VMASK_TRY(hipGetLastError()); return VRG_OK; }
     VMASK_GRAB(c.sizes, (size_t)c.ncomp + 1, "component sizes");
     VMASK_TRY(hipMemset(c.sizes, 0, ((size_t)c.ncomp + 1) * 8));
     k_cc_sizes<<<grid_for(((uint64_t)V + 3) / 4), TPB>>>(c.root, c.rank(), c.sizes, V);
@@ -614,6 +617,24 @@ bool shape_in_envelope(int64_t n0, int64_t n1, int64_t n2) {
     return !(n0 < 1 || n1 < 1 || n2 < 1 || (double)n0 * n1 * n2 >= 2147483000.0 || n0 > 32000 || n1 > 32000 || n2 > 32000);
 }
 int check_args(int device, int64_t n0, int64_t n1, int64_t n2) { Dims d; return check(device, n0, n1, n2, d); }
+// (vmask_cc.h: for vbrain_device.hip)
+int cc_label(const uint8_t* dvol, int32_t n0, int32_t n1, int32_t n2, int connectivity, bool with_sizes, CcOut& out) {
+    DevMem mem;
+    CC c;
+    const int rc = cc_run(mem, dvol, Dims{n0, n1, n2}, connectivity, c, with_sizes);
+    if (rc) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); g_err = "labelling kernels failed"; return VRG_E_INTERNAL; }
+    mem.drop(c.parent); mem.drop(c.tmp);
+    out.root = c.root; out.bits = c.bits; out.off = c.off; out.sizes = c.sizes; out.ncomp = c.ncomp;
+    out.nowned = 0;
+    for (void* p : mem.owned) out.owned[out.nowned++] = p;       // (root, bits, off, sizes: the holder frees them)
+    mem.owned.clear();
+    return VRG_OK;
+}
+void cc_release(CcOut& out) {
+    for (int i = 0; i < out.nowned; i++) (void)hipFree(out.owned[i]);
+    out = CcOut();
+}
 }  // namespace vmask
 
 extern "C" {

@@ -590,6 +590,92 @@ int vmask_reg_resample(int device, const void* moving, int dtype, int64_t m0, in
 int vmask_reg_hold(int device, const void* host /* may be NULL */, int64_t bytes, void** held);
 void vmask_reg_release(void* held);
 
+/* Skull stripping: the brain mask of a head volume, by a definition of our own (the reference leaves the step to an atlas-based GUI
+ * plugin; no parity with it is claimed).  Atlas-free, after the Brain Surface Extractor recipe: Marr-Hildreth edges, erosion, the
+ * main component, dilation, closing, hole filling.  Only a brain that is BRIGHTER than what surrounds it is supported.
+ * All floating-point work is float64, EVERY OPERATION ONE IEEE DOUBLE OPERATION IN THE WRITTEN ASSOCIATION, nothing contracted into
+ * an FMA; integer work is exact; the only atomics are integer ones.  Volumes are C-contiguous (i0, i1, i2), VRG_F32 or VRG_F64 (a
+ * float32 value is converted to double when read); a voxel that is not finite is refused (VRG_E_ARG).  Masks are uint8, non-zero =
+ * set; outputs hold 0 and 1.  Every array may be a host or a device pointer.  An optional Perona-Malik diffusion (vmask_diffuse)
+ * in front, and the floor and the contrast below, are the caller's (brain.py):
+ *
+ * Floor and contrast (host, from the 256 counts c of vmask_brain_histogram, in float64).  w = (hi - lo) / 256, N = sum c,
+ * W0[t] = sum_{k<=t} c_k, W1 = N - W0, m[t] = sum_{k<=t} k c_k, M = m[255].  t* = the first maximum over t = 0..254 of
+ * ((m W1 - (M - m) W0)^2) / (W0 W1), 0 where a class is empty (Otsu).  floor = lo + (t* + 1) w;
+ * contrast = (mu1 - mu0) w with mu0 = m[t*] / W0[t*], mu1 = (M - m[t*]) / W1[t*] (0 where a class is empty).
+ *
+ * Packed bit volumes (internal): 64 voxels of a row along axis 2 per 64-bit word, voxel i2 at bit i2 % 64 of word i2 / 64, rows
+ * padded to whole words, padding bits 0. */
+
+/* lo = min, hi = max of the volume (exact), counts[b] = the number of voxels with
+ *     b = min(255, floor((v - lo) * s)),  s = 256.0 / (hi - lo)   (s formed once on the host; v - lo, the product, floor: one operation each).
+ * lo, hi: one double each; counts: 256 unsigned 64-bit integers.  Counted with 32-bit atomics on LDS counters per workgroup, added
+ * to the 64-bit counts once per workgroup: integers, so no order matters and repeats are identical.
+ * VRG_E_ARG, before anything is written: a dtype other than the two; a null pointer; a shape outside the envelope of the other
+ * passes; and, found on the device: a voxel that is not finite, hi == lo. */
+int vmask_brain_histogram(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, double* lo, double* hi, uint64_t* counts /* 256 */);
+
+/* The scale-normalised Laplacian of Gaussian  E = sum_a (sigma^2 / h_a^2) d_a^2 (G_sigma * J),  spacing h (NULL: 1 1 1), sigma in
+ * the units of the spacing.  Taps per axis (host, double), s = sigma / h_a, r = (int)(4.0 * s + 0.5), which must lie in 1..64:
+ *     e[x] = exp(-0.5 * x * x / (s * s)) for x = -r..r;  S = their sum, ascending from 0.0;  phi[x] = e[x] / S;
+ *     phi2[x] = (x * x / (s * s * s * s) - 1.0 / (s * s)) * phi[x].
+ * A pass along an axis with taps w:  out[i] = sum over k = -r..r ascending, from +0.0, of w[k] * in[clamp(i - k, 0, n - 1)], one
+ * multiplication and one addition per tap.  Axis 2: A0 = phi * J, A2 = phi2 * J.  Axis 1: B00 = phi * A0, B20 = phi2 * A0,
+ * B02 = phi * A2.  Axis 0: T0 = phi2 * B00, T1 = phi * B20, T2 = phi * B02.  With c_a = (sigma * sigma) / (h_a * h_a):
+ *     E = (c_0 * T0 + c_1 * T1) + c_2 * T2.
+ * out: float64.  The result depends on the host's exp only through the taps (tests/brain_model.py restates everything else one
+ * numpy operation per operation).  Five float64 volumes of work space at the peak.
+ * VRG_E_ARG, before anything is written: a sigma or spacing that is not finite and positive or gives a radius outside 1..64; a
+ * dtype other than the two; a null pointer; a shape outside the envelope; a voxel that is not finite. */
+int vmask_brain_log(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
+                    double sigma, double* out);
+
+/* `steps` steps of erosion (op 0) or dilation (op 1) by the 6-neighbour cross: scipy.ndimage.binary_erosion / binary_dilation with
+ * generate_binary_structure(3, 1), iterations=steps, border_value=border.  Voxels outside the volume count as `border` for an
+ * erosion (0 or 1) and as 0 for a dilation (border must be 0).  steps == 0 copies.  One launch per step on the packed volume.
+ * VRG_E_ARG, before anything is written: op not 0 or 1; steps outside 0..100000; border not 0 or 1, or 1 with a dilation; a null
+ * pointer; a shape outside the envelope. */
+int vmask_binary_morph(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, int op /* 0 erode, 1 dilate */, int steps,
+                       int border /* 0 | 1, erosion only */, uint8_t* out);
+
+/* The largest connected component of the mask (connectivity 1, 2, 3 as vmask_label: 6, 18, 26 neighbours); among equals the one
+ * whose first voxel in raster order comes first (the smallest label of scipy.ndimage.label).  seed >= 0 (a raster index): the
+ * component that holds that voxel instead; VRG_E_ARG when the voxel is not set.  *size (may be NULL): its number of voxels.  An
+ * empty mask gives zeros and size 0.  Sizes are counted wave-aggregated (one atomic for the lanes of a wave that share a component).
+ * VRG_E_ARG, before anything is written: connectivity outside 1..3; a seed outside -1 .. n0 n1 n2 - 1; a null pointer; a shape
+ * outside the envelope. */
+int vmask_largest_component(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, int connectivity, int64_t seed /* or -1 */,
+                            uint8_t* out, int64_t* size /* may be NULL */);
+
+/* scipy.ndimage.binary_fill_holes(mask): every 6-connected component of the complement that has no voxel on a face of the volume
+ * is added (a cavity that reaches the outside only across a diagonal is filled).
+ * VRG_E_ARG: a null pointer; a shape outside the envelope. */
+int vmask_fill_holes(int device, const uint8_t* mask, int64_t n0, int64_t n1, int64_t n2, uint8_t* out);
+
+/* Steps 3-7 of the extraction on a volume J, packed from the candidate to the final unpack:
+ *   candidate     C = ((double) J > floor) & (E <= threshold), E as vmask_brain_log, written as bits by the last edge pass (E itself
+ *                 is never stored); threshold = edge * contrast.  The edge response of a bright body is positive in the dark gap
+ *                 just outside it: a positive threshold removes that rim and keeps flat interiors, where E is next to 0 and never above it
+ *                 (the truncated taps of phi'' sum to about -7e-5 at s = 1: E = -2.2e-4 of a flat intensity).
+ *   eroded        `erosion` steps of the cross, the outside counting as 0;
+ *   main          its largest 6-connected component (ties: the first in raster order), or the one that holds voxel `seed` (>= 0;
+ *                 VRG_E_ARG when that voxel is not in the eroded set); then `erosion` steps of dilation;
+ *   closed        `closing` steps of dilation, then `closing` steps of erosion with the outside counting as 1 (a brain that
+ *                 touches a face of a cropped scan is not eaten there);
+ *   final         the holes filled.
+ * out: uint8.  stages (may be NULL): 5 volumes of n0 n1 n2 bytes - candidate, eroded, main (before its dilation), closed, final.
+ * info (may be NULL): 16 int64 - [0..4] the set voxels of the five stages, [5] the peak of the call's own device allocations in
+ * bytes, [6] the number of components of the eroded set, [7] the size of the kept one, [8..13] the microseconds between HIP events
+ * around the edge passes, the erosion, the main component (unpack, labelling, sizes, selection), the dilation and the closing, the
+ * hole filling and the final unpack - the copies of `stages` included where asked for -, [14] those of the size pass alone, [15] 0.
+ * The edge passes' float64 volumes are freed before anything is labelled.
+ * VRG_E_ARG, before anything is written: sigma / spacing as vmask_brain_log; a threshold that is a NaN; a floor that is not
+ * finite; erosion or closing outside 0..1000; a seed outside -1 .. n0 n1 n2 - 1; a dtype other than the two; a null volume or out;
+ * a shape outside the envelope; a voxel that is not finite.  VRG_E_MEM: the work space does not fit the device. */
+int vmask_brain_extract(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
+                        double sigma, double threshold, double floor, int erosion, int closing, int64_t seed /* or -1 */, uint8_t* out,
+                        uint8_t* stages /* may be NULL */, int64_t* info /* 16, may be NULL */);
+
 const char* vmask_last_error(void);
 
 #ifdef __cplusplus
