@@ -26,6 +26,7 @@
 #include "../../include/vrg.h"
 #include "vmask_common.h"
 #include "vmask_host.h"
+#include "vreg_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -38,14 +39,6 @@ constexpr int MINB = 8, MAXB = 128;
 static_assert(RG == RT, "a thread takes one voxel per trip");
 
 struct RegMap { double t[12]; };                   // the first three rows of T: fixed voxel -> moving voxel
-struct Ext { int n0, n1, n2; };
-
-__device__ __forceinline__ void split(int64_t v, const Ext n, int& i, int& j, int& k) {
-    const unsigned u = (unsigned)v, plane = (unsigned)n.n1 * (unsigned)n.n2;       // (fewer than 2^31 voxels)
-    const unsigned a = u / plane, r = u - a * plane, b = r / (unsigned)n.n2;
-    i = (int)a; j = (int)b; k = (int)(r - b * (unsigned)n.n2);
-}
-
 __device__ __forceinline__ double coord(const RegMap& M, int a, int i, int j, int k) {
     return ((M.t[4 * a] * (double)i + M.t[4 * a + 1] * (double)j) + M.t[4 * a + 2] * (double)k) + M.t[4 * a + 3];
 }
@@ -88,7 +81,7 @@ __global__ void __launch_bounds__(RT) k_reg_hist(const uint8_t* __restrict__ fb,
     // the voxel's index is split once and then advanced by the split stride: no division per voxel
     const int64_t stride = (int64_t)gridDim.x * RG;
     int i, j, k, di, dj, dk;
-    split(stride, n, di, dj, dk);                  // (dj < n1, dk < n2: at most one carry per axis below)
+    split(stride, n, di, dj, dk);                  // (dj < n1, dk < n2: at most one carry per axis, vreg_walk.h)
     int64_t v = (int64_t)blockIdx.x * RG + threadIdx.x;
     split(v, n, i, j, k);
     for (; v < V; v += stride) {
@@ -97,11 +90,7 @@ __global__ void __launch_bounds__(RT) k_reg_hist(const uint8_t* __restrict__ fb,
             double value;
             if (sample<T>(mov, m, M, i, j, k, value)) atomicAdd(&counts[bf * B + bin_of(value, mlo, ms, B)], 1u);
         }
-        k += dk;
-        if (k >= n.n2) { k -= n.n2; j++; }
-        j += dj;
-        if (j >= n.n1) { j -= n.n1; i++; }
-        i += di;
+        advance_split(n, di, dj, dk, i, j, k);
     }
     __syncthreads();
     for (int s = threadIdx.x; s < slots; s += RT)

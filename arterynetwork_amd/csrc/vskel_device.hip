@@ -17,7 +17,7 @@
 // (a wave works inside one row, so the subfield of its k-th voxels is the same in every lane: two ballots and one atomic
 // per wave and subfield); then eight launches of k_skel_step, launch s over list s: the 26 neighbours gathered into one
 // register word (bit a*9 + b*3 + c for the offset (a-1, b-1, c-1)), the end-point test a popcount, both component counts
-// flood fills by shifts and masks of that word - no table.  Launch s stores only to voxels of subfield s and loads only
+// flood fills by shifts and masks of that word - no table (vskel_simple.h, which a host program enumerates).  Launch s stores only to voxels of subfield s and loads only
 // voxels of other subfields: no race, no fence; the kernel boundary orders the steps.  The host reads one deletion counter
 // per cycle.
 #include <hip/hip_runtime.h>
@@ -30,6 +30,7 @@
 #include "../../include/vrg.h"
 #include "vmask_common.h"
 #include "vmask_host.h"
+#include "vskel_simple.h"
 
 namespace {
 
@@ -129,39 +130,6 @@ __global__ void __launch_bounds__(TPB) k_skel_mark(const uint8_t* __restrict__ P
             if (b) list[at + na + lanes_below(mb)] = first + q + 2;
         }
     }
-}
-
-// ---- the 3x3x3 neighbourhood as a 27-bit word: bit a*9 + b*3 + c
-constexpr uint32_t N_ALL = (1u << 27) - 1u, N_CENTRE = 1u << 13;
-constexpr uint32_t C0 = 0x1249249u, C2 = C0 << 2;                       // c == 0 / c == 2
-constexpr uint32_t B0 = 0x7u | (0x7u << 9) | (0x7u << 18), B2 = B0 << 6;   // b == 0 / b == 2
-constexpr uint32_t N_FACE = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);
-constexpr uint32_t N_CORNER = (1u << 0) | (1u << 2) | (1u << 6) | (1u << 8) | (1u << 18) | (1u << 20) | (1u << 24) | (1u << 26);
-constexpr uint32_t N_18 = N_ALL & ~N_CORNER & ~N_CENTRE;
-
-// the neighbours of x (bits 0..26 only) one step along c, along b, along a: what a shift carries into the next row, plane or
-// past bit 26 is masked off
-__device__ __forceinline__ uint32_t step_c(uint32_t x) { return ((x << 1) & (N_ALL & ~C0)) | ((x >> 1) & ~C2); }
-__device__ __forceinline__ uint32_t step_b(uint32_t x) { return ((x << 3) & (N_ALL & ~B0)) | ((x >> 3) & ~B2); }
-__device__ __forceinline__ uint32_t step_a(uint32_t x) { return ((x << 9) & N_ALL) | (x >> 9); }
-// the part of `set` that is 26-connected (a box dilation: the three axes one after the other) / 6-connected to `seed`
-__device__ __forceinline__ uint32_t fill26(uint32_t seed, uint32_t set) {
-    uint32_t x = seed, y;
-    do { y = x; x |= step_c(x); x |= step_b(x); x |= step_a(x); x &= set; } while (x != y);
-    return x;
-}
-__device__ __forceinline__ uint32_t fill6(uint32_t seed, uint32_t set) {
-    uint32_t x = seed, y;
-    do { y = x; x = (x | step_c(x) | step_b(x) | step_a(x)) & set; } while (x != y);
-    return x;
-}
-// object bits of N26* -> may the centre be deleted (not an end point, simple)
-__device__ __forceinline__ bool deletable(uint32_t obj) {
-    if (__popc(obj) < 2) return false;                                  // end point; an isolated voxel is not simple
-    if (fill26(obj & (0u - obj), obj) != obj) return false;             // more than one 26-component of the object
-    const uint32_t bg = ~obj & N_18, face = bg & N_FACE;
-    if (!face) return false;
-    return (fill6(face & (0u - face), bg) & face) == face;             // every background face neighbour reached inside N18*
 }
 
 // step s of a cycle: one thread per listed voxel of subfield s

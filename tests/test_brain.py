@@ -340,6 +340,49 @@ def test_histogram_is_numpys(dtype):
             BR.intensityFloor(bad)
 
 
+# ---- k_brain_minmax and k_brain_hist are capped at 1024 workgroups of 256 threads: voxels from 262 144 on are met on a second turn
+SECOND_TURN = 1024 * 256
+LATE_SHAPE = (5, 210, 257)                                 # 269 850 voxels: the last 7 706 on the second turn
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', [np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+def test_histogram_is_numpys_on_the_second_turn(dtype):
+    """269 850 voxels > 262 144: the minimum and the maximum are voxels that only the second turn of k_brain_minmax sees, and the
+    256 counts, which k_brain_hist's second turn adds to, are numpy's and sum to V."""
+    V = int(np.prod(LATE_SHAPE))
+    assert SECOND_TURN < V < 2 * SECOND_TURN
+    v = _noisy(LATE_SHAPE, seed=7).astype(dtype)
+    v.flat[SECOND_TURN + 5], v.flat[V - 2] = v.min() - 50.0, v.max() + 50.0
+    assert int(v.argmin()) == SECOND_TURN + 5 and int(v.argmax()) == V - 2
+    before = v.copy()
+    fl, contrast, lo, hi, counts = BR.intensityFloor(v)
+    rlo, rhi, rcounts = M.histogram(v)
+    assert (lo, hi) == (rlo, rhi) == (float(v.flat[SECOND_TURN + 5]), float(v.flat[V - 2]))
+    assert counts.dtype == np.uint64 and np.array_equal(counts, rcounts) and int(counts.sum()) == V
+    assert (fl, contrast) == M.floor_contrast(rcounts, rlo, rhi)[:2] and np.array_equal(v, before)
+    # the same volume with the first turn's voxels alone gives other counts: the second turn's voxels are in these
+    assert not np.array_equal(np.bincount(np.minimum(255.0, np.floor((v.ravel()[:SECOND_TURN].astype(np.float64) - lo) * (256.0 / (hi - lo)))).astype(np.int64), minlength=256), rcounts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('value', [np.nan, np.inf, -np.inf], ids=['nan', 'inf', '-inf'])
+def test_a_voxel_that_is_not_finite_on_the_second_turn_is_refused(value):
+    """One NaN (Inf) at a raster index >= 262 144, which only the second turn of k_brain_minmax meets: every entry refuses."""
+    for dtype, at in ((np.float32, SECOND_TURN), (np.float64, int(np.prod(LATE_SHAPE)) - 1), (np.float32, SECOND_TURN + 4321)):
+        v = _noisy(LATE_SHAPE, seed=8).astype(dtype)
+        assert np.isfinite(v).all()
+        v.flat[at] = value
+        with pytest.raises(VrgError):
+            BR.intensityFloor(v)
+        with pytest.raises(VrgError):
+            BR.laplacianOfGaussian(v)
+        with pytest.raises(VrgError):
+            BR.brainExtraction(v)
+        with pytest.raises(VrgError):
+            BR.brainExtraction(v, floor=50.0)
+
+
 # ------------------------------------------------------------------ GPU: the edge response
 def _log_case(shape, sigma, spacing, dtype, seed=0):
     I = _noisy(shape, seed).astype(dtype)
@@ -371,6 +414,15 @@ def test_log_is_the_model_at_the_tile_extents(shape):
     for i, spacing in enumerate(SPACINGS):
         _log_case(shape, 1.0, spacing, (np.float64, np.float32, np.float64)[i], seed=i)
     _log_case(shape, 2.6, None, np.float32, seed=5)                        # radius 10: wider than a thread's 8 rows / planes
+
+
+@pytest.mark.gpu
+def test_log_is_the_model_beyond_32768_rows():
+    """129 x 255 = 32 895 rows > 32 768: k_brain_axis2's workgroups fill a second row of the grid, rows 32 768 .. 32 894."""
+    shape = (129, 255, 3)
+    assert shape[0] * shape[1] > 32768
+    _log_case(shape, 1.0, None, np.float32, seed=6)
+    _log_case(shape, 1.0, (0.5, 0.7, 1.3), np.float64, seed=7)
 
 
 @pytest.mark.gpu
@@ -460,6 +512,74 @@ def test_largest_component_ties_empty_and_full():
     d = np.zeros((3, 3, 3), np.uint8)
     d[0, 0, 0] = d[0, 1, 1] = d[1, 1, 1] = 1
     assert BR.largestComponent(d, 1).sum() == 2 and BR.largestComponent(d, 2).sum() == 3 and BR.largestComponent(d, 3).sum() == 3
+
+
+# ---- k_brain_sizes: 2048 workgroups x 4 waves = 8192 waves, each a contiguous run of ceil(trips / 8192) trips of 64 voxels.  Above
+# 524 288 voxels a run holds two trips and the wave carries the counts it holds from one trip into the next.
+SIZES_SHAPE = (20, 160, 170)                               # 544 000 voxels = 8500 trips: runs of 2 trips, 128 voxels
+
+
+def _check_largest(m, connectivity=1, label=''):
+    ref, size, _ = M.largest(m, STRUCTURES[connectivity])
+    n = []
+    got = BR.largestComponent(m, connectivity, size=n)
+    assert got.dtype == np.uint8 and np.array_equal(got, ref) and n == [size], (label, connectivity, n, size)
+    return got, size
+
+
+def test_sizes_shape_gives_every_wave_two_trips():
+    V = int(np.prod(SIZES_SHAPE))
+    trips = -(-V // 64)
+    assert V > 2048 * 4 * 64 and -(-trips // (2048 * 4)) == 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('connectivity', [1, 2, 3])
+def test_largest_component_is_scipys_when_a_wave_takes_two_trips(connectivity):
+    """544 000 voxels, p = 0.3: under 6 neighbours 33 537 components, the largest of 1292 and 1108 voxels; under 18 and 26 one that
+    runs through the whole volume and so through every wave's run.  Also a seed in a small component, and one on the background."""
+    m = (np.random.default_rng(3).random(SIZES_SHAPE) < 0.3).astype(np.uint8)
+    before = m.copy()
+    got, size = _check_largest(m, connectivity, 'random 0.3')
+    lab, ncomp = ndi.label(m, STRUCTURES[connectivity])
+    sizes = np.bincount(lab.ravel())[1:]
+    if connectivity == 1:
+        assert ncomp == 33537 and sorted(sizes)[-2:] == [1108, 1292] and size == 1292
+    else:
+        assert size > m.sum() // 2
+    for small in (int(np.argmin(sizes)) + 1, int(np.argsort(sizes, kind='stable')[len(sizes) // 2]) + 1, ncomp):      # the last label lies at the volume's end
+        at = tuple(int(x) for x in np.argwhere(lab == small)[-1])
+        n = []
+        assert np.array_equal(BR.largestComponent(m, connectivity, seed=at, size=n), lab == small) and n == [int(sizes[small - 1])], small
+    with pytest.raises(VrgError):
+        BR.largestComponent(m, connectivity, seed=tuple(int(x) for x in np.argwhere(m == 0)[-1]))
+    assert np.array_equal(m, before)
+
+
+@pytest.mark.gpu
+def test_largest_component_tie_and_slab_across_the_waves_runs():
+    V = int(np.prod(SIZES_SHAPE))
+    # two equal largest components in a sprinkle of small ones; the second in raster order lies wholly in the volume's second half, so
+    # other waves count it: the first one wins
+    m = (np.random.default_rng(4).random(SIZES_SHAPE) < 0.05).astype(np.uint8)
+    m[0:3, 0:8, 0:45] = 0
+    m[14:17, 98:106, 48:89] = 0
+    m[1, 2:6, 3:40] = 1                                                    # 148 voxels, from raster index 27 543 on
+    m[15, 100:104, 50:87] = 1                                              # 148 voxels, from raster index 425 050 on
+    assert np.ravel_multi_index((15, 100, 50), SIZES_SHAPE) > V // 2 > 524288 // 2 > np.ravel_multi_index((1, 5, 39), SIZES_SHAPE)
+    sizes = np.bincount(ndi.label(m, STRUCTURES[1])[0].ravel())[1:]
+    assert sorted(sizes)[-2:] == [148, 148] and sorted(sizes)[-3] < 148
+    got, size = _check_largest(m, 1, 'tie')
+    assert size == 148 and got[1, 2:6, 3:40].all() and got.sum() == 148 and not got[15].any()
+    flipped = m[::-1, ::-1, ::-1].copy()                                   # now the other box is met first
+    got, size = _check_largest(flipped, 1, 'tie, flipped')
+    assert size == 148 and got[4, 56:60, 83:120].all() and got.sum() == 148
+    # a slab through the whole volume: every row of it, 170 voxels, crosses the boundary between two waves' runs of 128
+    s = (np.random.default_rng(5).random(SIZES_SHAPE) < 0.2).astype(np.uint8)
+    s[:, 80, :] = 1
+    for connectivity in (1, 3):
+        got, size = _check_largest(s, connectivity, 'slab')
+        assert got[:, 80, :].all() and size >= 20 * 170
 
 
 # ------------------------------------------------------------------ GPU: hole filling

@@ -1,5 +1,6 @@
 """Edge-preserving denoising (DESIGN.md section 9 entry f14): the numpy model tests/denoise_model.py is checked on the CPU
-(what the filters are for, range, mean, fixed points, the explicit median against scipy), then vmask_diffuse must return
+(what the filters are for, range, mean, fixed points, the explicit median against scipy), the median's exchange networks are proved on
+every 0/1 input, then vmask_diffuse must return
 the model's bits with the rational conductance and stay within 1e-9 of the input's span with the exponential one, and
 vmask_median must equal scipy.ndimage.median_filter(mode='nearest')."""
 import functools
@@ -209,6 +210,69 @@ def test_denoise_kernels_use_no_scratch(tmp_path):
         # the first build: k_den_diffuse 82 (rational) and 98 (exponential); k_den_median 8 .. 64 for the windows of 1, 3 and 9
         # values, 127 (float32) and 126 (float64) for the window of 27
         assert vgprs <= 128, '%s uses %d VGPRs' % (name, vgprs)
+
+
+# ------------------------------------------------------------------ no GPU needed: the median's exchange networks, proved
+NET_COMPARATORS = {3: 3, 9: 24, 27: 126}                 # a change to a table is a decision: it shows up here
+
+
+def _networks():
+    """NET3, NET9 and NET27 as they stand in vden_device.hip: {N: [(a, b), ...]}."""
+    text = open(os.path.join(ROOT, 'arterynetwork_amd', 'csrc', 'vden_device.hip')).read()
+    nets = {}
+    for m in re.finditer(r'constexpr CE NET(\d+)\[\] = \{(.*?)\};', text, re.S):
+        body = m.group(2)
+        pairs = [(int(a), int(b)) for a, b in re.findall(r'\{\s*(\d+)\s*,\s*(\d+)\s*\}', body)]
+        assert not re.sub(r'\{\s*\d+\s*,\s*\d+\s*\}|[\s,]', '', body), 'NET%s holds something that is no comparator' % m.group(1)
+        nets[int(m.group(1))] = pairs
+    return text, nets
+
+
+def _popcounts(x):
+    x = x.astype(np.uint64)
+    c = np.zeros(x.shape, np.int64)
+    for s in range(0, 32):
+        c += ((x >> np.uint64(s)) & np.uint64(1)).astype(np.int64)
+    return c
+
+
+@pytest.mark.parametrize('N', [3, 9, 27])
+def test_median_network_selects_the_median_of_every_01_input(N):
+    """The 0-1 principle, exhaustively: the pruned Batcher network NET<N> of vden_device.hip is applied to all 2^N inputs of zeros
+    and ones, bit-sliced (one bit per input, a comparator (a, b) is (a & b, a | b) since `exchange` leaves the minimum in a), and
+    wire N // 2 must be 1 exactly where the input holds at least N // 2 + 1 ones.  A network of min / max exchanges commutes with
+    every monotone map, so a network that selects the median of every 0/1 input selects it for every input of totally ordered
+    values: this proves the median for every finite window, ties included.  It covers orderings only - a NaN is not ordered, and
+    include/vmask.h says of vmask_median's volume "assumed finite".  NET27 (2^27 inputs) takes about 1 s."""
+    text, nets = _networks()
+    assert sorted(nets) == [3, 9, 27]
+    net = nets[N]
+    assert len(net) == NET_COMPARATORS[N]
+    assert all(a < b < N for a, b in net), [c for c in net if not c[0] < c[1] < N]
+    assert re.search(r'a = lo; b = hi;', text) and 'return v[N / 2];' in text            # what the proof assumes of exchange and median_of
+    # input x (an N-bit number) has bit i on wire i; bit b of word w is input 64 w + b
+    low = [np.uint64(sum(1 << b for b in range(64) if (b >> i) & 1)) for i in range(6)]
+    at_least = [np.uint64(sum(1 << b for b in range(64) if bin(b).count('1') >= k)) for k in range(8)]      # [7] = 0
+    words = max(1, (1 << N) >> 6)
+    valid = np.uint64((1 << min(64, 1 << N)) - 1)                                        # N = 3: one word, 8 inputs
+    chunk = min(words, 1 << 16)
+    ones, checked = np.uint64(0xFFFFFFFFFFFFFFFF), 0
+    for start in range(0, words, chunk):
+        w = np.arange(start, start + chunk, dtype=np.uint64)
+        wires = []
+        for i in range(N):
+            if i < 6:
+                wires.append(np.full(chunk, low[i], np.uint64))
+            else:
+                wires.append(np.where((w >> np.uint64(i - 6)) & np.uint64(1), ones, np.uint64(0)))
+        for a, b in net:
+            wires[a], wires[b] = wires[a] & wires[b], wires[a] | wires[b]
+        need = np.clip(N // 2 + 1 - _popcounts(w), 0, 7)                                  # ones still needed among the word's 6 low wires
+        want = np.array(at_least, np.uint64)[need]
+        wrong = (wires[N // 2] ^ want) & valid
+        assert not wrong.any(), 'NET{}: input {:#x} gives the wrong middle value'.format(N, int(np.flatnonzero(wrong)[0] + start) * 64)
+        checked += chunk * min(64, 1 << N)
+    assert checked == 1 << N
 
 
 # ------------------------------------------------------------------ GPU: diffusion against the model

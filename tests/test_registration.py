@@ -1,6 +1,6 @@
 """Rigid and affine registration (DESIGN.md section 9 entry f16).  On the CPU: the host cost entry against its numpy restatement,
 paramsToMatrix, what the step is for on the numpy model tests/registration_model.py alone, the refusals, the kernels' resource
-records.  On the GPU: the joint histogram must return the model's counts, the extrema, bin images, pyramids and resampled volumes
+records, the histogram's walk (csrc/vreg_walk.h) against the split of every voxel it visits.  On the GPU: the joint histogram must return the model's counts, the extrema, bin images, pyramids and resampled volumes
 the model's bits, and ``register`` the model's matrix and trace bit for bit."""
 import functools
 import os
@@ -358,6 +358,132 @@ def test_registration_kernels_use_no_scratch(tmp_path):
         assert vgprs <= 48, '%s uses %d VGPRs' % (name, vgprs)
 
 
+# ------------------------------------------------------------------ no GPU needed: the histogram's walk
+# A stand-alone host program over csrc/vreg_walk.h, the code k_reg_hist runs: from every start below the stride, advance_split must
+# reproduce split(v) - and both the plain quotients and remainders of v - at every trip up to V.  argv: n0 n1 n2, repeated.
+# Per shape and stride it prints the steps checked and, of the advances into a live trip, how many carried on k, on j, on both.
+WALK_PROGRAM = r"""
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include "vreg_walk.h"
+
+int main(int argc, char** argv) {
+    const int64_t groups[] = {1, 2, 3, 7, 1024};
+    long bad = 0;
+    for (int a = 1; a + 2 < argc; a += 3) {
+        const Ext n{std::atoi(argv[a]), std::atoi(argv[a + 1]), std::atoi(argv[a + 2])};
+        const int64_t V = (int64_t)n.n0 * n.n1 * n.n2;
+        for (int64_t g : groups) {
+            const int64_t stride = g * 256;
+            int di, dj, dk;
+            split(stride, n, di, dj, dk);
+            if (dj >= n.n1 || dk >= n.n2 || ((int64_t)di * n.n1 + dj) * n.n2 + dk != stride) { std::printf("split of the stride is wrong\n"); bad++; }
+            long long steps = 0, ck = 0, cj = 0, cb = 0, trips = 0;
+            for (int64_t start = 0; start < stride && start < V; start++) {
+                int i, j, k;
+                split(start, n, i, j, k);
+                long long t = 0;
+                for (int64_t v = start; v < V; v += stride) {
+                    const int64_t wi = v / ((int64_t)n.n1 * n.n2), wj = (v / n.n2) % n.n1, wk = v % n.n2;
+                    int si, sj, sk;
+                    split(v, n, si, sj, sk);
+                    if (i != wi || j != wj || k != wk || si != wi || sj != wj || sk != wk) {
+                        if (bad < 5) std::printf("(%d, %d, %d) stride %lld voxel %lld: walked (%d, %d, %d), split (%d, %d, %d), is (%lld, %lld, %lld)\n", n.n0, n.n1, n.n2,
+                                                 (long long)stride, (long long)v, i, j, k, si, sj, sk, (long long)wi, (long long)wj, (long long)wk);
+                        bad++;
+                    }
+                    steps++; t++;
+                    if (v + stride < V) {
+                        const bool kc = k + dk >= n.n2, jc = j + (kc ? 1 : 0) + dj >= n.n1;
+                        ck += kc; cj += jc; cb += kc && jc;
+                    }
+                    advance_split(n, di, dj, dk, i, j, k);
+                }
+                if (t > trips) trips = t;
+            }
+            std::printf("walk %d %d %d %lld steps %lld trips %lld carries %lld %lld %lld\n", n.n0, n.n1, n.n2, (long long)stride, steps, trips, ck, cj, cb);
+        }
+    }
+    std::printf(bad ? "FAILED %ld\n" : "OK\n", bad);
+    return bad ? 1 : 0;
+}
+"""
+
+CARRY_SHAPES = [(70, 61, 63), (130, 64, 65)]             # k_reg_hist takes carries on its second (and third) trip: test_carry_shapes_take_carries
+WALK_SHAPES = [(3, 5, 17477)] + CARRY_SHAPES + [(9, 241, 121), (1, 1, 262145), (641, 409, 1), (263, 1, 997), (2, 2, 2),
+                                                 (1, 211, 307), (97, 1, 701), (211, 307, 1),                      # each extent 1
+                                                 (5, 7, 11), (30, 29, 30), (13, 30, 5), (23, 6, 29), (17, 17, 17)]   # trips in the hundreds at g = 1
+
+
+def _walk_carries(n, stride=None):
+    """A restatement of k_reg_hist's walk in numpy, every start at once: (trips, and of the advances into a live trip the number that
+    carry on k, on j, on both at once).  The stride is the kernel's: min(ceil(V / G), WORKGROUPS) workgroups of G voxels.
+    The walked (i, j, k) is checked against the quotients and remainders at every trip."""
+    n0, n1, n2 = n
+    V = n0 * n1 * n2
+    S = min(-(-V // G), WORKGROUPS) * G if stride is None else stride
+    di, dj, dk = S // (n1 * n2), (S // n2) % n1, S % n2
+    v = np.arange(min(S, V), dtype=np.int64)
+    i, j, k = v // (n1 * n2), (v // n2) % n1, v % n2
+    trips, ck, cj, cb = 0, 0, 0, 0
+    while len(v):
+        trips += 1
+        assert np.array_equal(i, v // (n1 * n2)) and np.array_equal(j, (v // n2) % n1) and np.array_equal(k, v % n2), (n, trips)
+        live = v + S < V
+        k = k + dk
+        kc = k >= n2
+        k, j = np.where(kc, k - n2, k), j + kc + dj
+        jc = j >= n1
+        j, i = np.where(jc, j - n1, j), i + jc + di
+        ck, cj, cb = ck + int((kc & live).sum()), cj + int((jc & live).sum()), cb + int((kc & jc & live).sum())
+        keep = live
+        v, i, j, k = (v + S)[keep], i[keep], j[keep], k[keep]
+    return trips, ck, cj, cb
+
+
+def test_carry_shapes_take_carries():
+    """Why (70, 61, 63) and (130, 64, 65) are in the GPU tests: on the kernel's own stride, 1024 x 256 = 262 144 = split (68, 13, 1) and
+    (63, 0, 64) there, voxels advance into a live second (third) trip with a carry on k, on j, and on both at once - at (130, 64, 65)
+    dj = 0, so every j carry is a j of exactly n1.  At (3, 5, 17477), the older two-trip case, the 11 voxels of the second trip
+    (k < 11, stride split (2, 4, 17466)) take none: a dropped or doubled carry would pass there."""
+    assert _walk_carries((3, 5, 17477)) == (2, 0, 0, 0)
+    assert _walk_carries((70, 61, 63)) == (2, 108, 820, 14)
+    assert _walk_carries((130, 64, 65)) == (3, 274368, 4224, 4224)
+    for n in CARRY_SHAPES:
+        assert int(np.prod(n)) > WORKGROUPS * G and min(_walk_carries(n)[1:]) > 0
+    assert (262144 // (64 * 65), (262144 // 65) % 64, 262144 % 65) == (63, 0, 64) and (262144 // (61 * 63), (262144 // 63) % 61, 262144 % 63) == (68, 13, 1)
+    assert 2 * 262144 < 130 * 64 * 65 < 3 * 262144 and 262144 < 70 * 61 * 63 < 2 * 262144
+
+
+def test_walk_reproduces_split_at_every_trip(tmp_path):
+    """csrc/vreg_walk.h on the host: every start below the stride, every trip up to V, strides g x 256 for g in 1, 2, 3, 7, 1024,
+    over WALK_SHAPES; the carries the program counts on the kernel's own stride are the restatement's."""
+    cxx = os.environ.get('CXX', 'g++')
+    src, exe = tmp_path / 'walk.cpp', tmp_path / 'walk'
+    src.write_text(WALK_PROGRAM)
+    p = subprocess.run([cxx, '-O1', '-std=c++17', '-I', os.path.join(ROOT, 'arterynetwork_amd', 'csrc'), '-o', str(exe), str(src)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = subprocess.run([str(exe)] + [str(e) for n in WALK_SHAPES for e in n], capture_output=True, text=True)
+    print(r.stdout[-6000:])
+    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-3000:]
+    rows = {}
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if f and f[0] == 'walk':
+            rows[(int(f[1]), int(f[2]), int(f[3])), int(f[4])] = (int(f[6]), int(f[8]), tuple(int(x) for x in f[10:13]))
+    assert len(rows) == 5 * len(WALK_SHAPES)
+    most = 0
+    for (n, stride), (steps, trips, carries) in rows.items():
+        V = int(np.prod(n))
+        assert steps == V and trips == -(-V // stride), (n, stride)                        # every voxel is on exactly one start's walk
+        assert (trips,) + carries == _walk_carries(n, stride), (n, stride)
+        most = max(most, trips)
+    assert most >= 1000 and sum(t >= 100 for _, t, _ in rows.values()) >= 10              # long walks: (1, 1, 262145) at g = 1 has 1025 trips
+    for n in CARRY_SHAPES:
+        assert rows[n, WORKGROUPS * G][1:] == (_walk_carries(n)[0], _walk_carries(n)[1:])
+
+
 # ------------------------------------------------------------------ GPU: the joint histogram
 def _volume(shape, kind, seed, dtype=np.float64):
     rng = np.random.default_rng(seed)
@@ -450,6 +576,52 @@ def test_joint_histogram_when_the_stride_loop_runs_twice():
     moving = _volume((4, 6, 301), 'noise', 4, np.float32)
     H, inside = _check_hist(fixed, moving, _scaled(n, moving.shape), 64, 'random', 'two trips')
     assert int(H.sum()) > 0.9 * inside and int(H.sum(axis=1).max()) > inside // 3       # the background's row holds its half
+
+
+def _turned(n, m, degrees=10.0, shrink=0.7):
+    """The fixed grid shrunk to `shrink` of the moving one's extent and turned about the two centres by `degrees` on every axis: no
+    coefficient of the map is zero, and at 0.7 every fixed voxel, the last ones in raster order too, lies inside the moving volume."""
+    rot = R.paramsToMatrix([0.0, 0.0, 0.0] + [np.deg2rad(degrees)] * 3, 6, np.zeros(3))[:3, :3]
+    scale = np.array([shrink * (m[a] - 1.0) / (n[a] - 1.0) if n[a] > 1 else 0.0 for a in range(3)])
+    T = np.eye(4)
+    T[:3, :3] = rot * scale[None, :]
+    T[:3, 3] = (np.array(m) - 1.0) / 2.0 - T[:3, :3] @ ((np.array(n) - 1.0) / 2.0)
+    return T
+
+
+def _inside_from(T, n, m, first):
+    """How many fixed voxels of raster index >= first the map puts inside the moving volume."""
+    p = M._coords(T, n)
+    inside = np.ones(n, bool)
+    for a in range(3):
+        inside &= (p[a] >= 0.0) & (p[a] <= m[a] - 1.0)
+    return int(inside.ravel()[first:].sum())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('n,dtype', [((70, 61, 63), np.float32), ((130, 64, 65), np.float64)], ids=['70x61x63-float32', '130x64x65-float64'])
+def test_joint_histogram_where_the_walk_carries(n, dtype):
+    """269 010 and 540 800 fixed voxels against the 262 144 of one trip of the whole grid: a second, and a third, trip whose voxels
+    advance with carries on k, on j and on both (test_carry_shapes_take_carries counts them: 108 / 820 / 14 and 274 368 / 4 224 /
+    4 224).  Under the turned maps a wrong i or j cannot hide behind a zero coefficient.  The stretched, the late half-voxel and the
+    turned map put voxels of every later trip inside the moving volume; the maps '_scaled + (0.5, -0.5, 0.5)' and '_rotated' are run
+    as well, though at (70, 61, 63) they leave the last two planes, which are the second trip, outside."""
+    assert n in CARRY_SHAPES
+    V, m = int(np.prod(n)), (22, 19, 21)
+    trips = -(-V // (WORKGROUPS * G))
+    fixed, moving = _volume(n, 'brain', 20), _volume(m, 'noise', 21, dtype)
+    maps = [('stretched', _scaled(n, m), True), ('half a voxel', _scaled(n, m, (0.5, -0.5, 0.5)), False), ('rotated', _rotated(n, m), False),
+            ('half a voxel, late', _scaled(n, m, (-0.5, 0.5, -0.5)), True), ('turned', _turned(n, m), True), ('turned, partly outside', _turned(n, m, 25.0, 1.1), True)]
+    for label, T, late in maps:
+        if late:                                             # the last trip counts voxels
+            assert _inside_from(T, n, m, (trips - 1) * WORKGROUPS * G) > 0, label
+        for B, mask in ((64, 'full'), (64, 'random')) + (((128, 'random'),) if label == 'turned' else ()):
+            H, inside = _check_hist(fixed, moving, T, B, mask, '{} {} B {} mask {}'.format(n, label, B, mask))
+            assert 0 < int(H.sum()) <= inside
+            if label in ('stretched', 'turned'):
+                assert int(H.sum()) == inside                    # every voxel of the mask is inside
+            if mask == 'full' and label != 'rotated':
+                assert int(H.sum()) == _inside_from(T, n, m, 0) > V // 3
 
 
 @pytest.mark.gpu
@@ -601,6 +773,89 @@ def test_resample_is_the_model(n):
     fA, mA = M.affine_of((1, 1, 2), (5, 6, 7)), M.affine_of((2, 1, 1), (4, 6, 8))
     mv = _volume((4, 6, 8), 'noise', 14)
     assert _same(R.resample(mv, (W, fA, mA), (5, 6, 7)), R.resample(mv, R.voxelMap(W, fA, mA), (5, 6, 7)))
+
+
+# ---- the second turn of the passes that are capped at WORKGROUPS workgroups of 256 threads: voxels from 262 144 on
+SECOND_TURN = WORKGROUPS * 256
+LATE_SHAPE = (70, 61, 63)                                  # 269 010 voxels: 6 866 of them, the planes i >= 68 and a little more, on the second turn
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', [np.float32, np.float64], ids=['float32', 'float64'])
+def test_extrema_and_quantise_on_the_second_turn(dtype):
+    """k_reg_minmax and k_reg_quantise at 269 010 voxels > 262 144: the minimum and the maximum lie on the second turn only, and a NaN,
+    an Inf and a voxel outside the mask out there get 255 and are not counted."""
+    n = LATE_SHAPE
+    V = int(np.prod(n))
+    assert SECOND_TURN < V < 2 * SECOND_TURN
+    v = _volume(n, 'brain', 30, dtype)
+    at_min, at_max, at_nan, at_inf, at_out = SECOND_TURN, V - 1, SECOND_TURN + 257, V - 300, SECOND_TURN + 3000
+    v.flat[at_min], v.flat[at_max], v.flat[at_nan], v.flat[at_inf] = -1234.5, 4321.0, np.nan, np.inf
+    mask = _mask('random', n, 31)
+    for at in (at_min, at_max, at_nan, at_inf):
+        mask.flat[at] = 1
+    mask.flat[at_out] = 0
+    early = mask.copy()
+    early.reshape(-1)[SECOND_TURN:] = 0
+    before = v.copy()
+    for label, m in (('no mask', None), ('mask', mask), ('a mask without the second turn', early)):
+        got, want = R.extrema(v, m), M.extrema(v, m)
+        assert got == want, (label, got, want)
+        assert (got == (-1234.5, 4321.0)) == (m is not early), label
+        for B in (64, 128):
+            s = R.binScale(want[0], want[1], B)
+            (gb, gi), (wb, wi) = R.quantise(v, want[0], s, B, m), M.quantise(v, want[0], s, B, m)
+            assert _same(gb, wb) and gi == wi, (label, B, int((gb != wb).sum()), gi, wi)
+            assert gb.flat[at_nan] == 255 and gb.flat[at_inf] == 255
+            if m is None:
+                assert gi == V - 2 and gb.flat[at_min] == 0 and gb.flat[at_max] == B - 1 and gb.flat[at_out] != 255
+            elif m is mask:
+                assert gi == int(mask.sum()) - 2 and gb.flat[at_out] == 255 and gb.flat[at_min] == 0 and gb.flat[at_max] == B - 1
+            else:
+                assert gi == int(early.sum()) and (gb.flat[SECOND_TURN:] == 255).all()
+    assert _same(v, before)
+
+
+@pytest.mark.gpu
+def test_resample_on_the_second_turn():
+    """k_reg_linear and k_reg_nearest at 269 010 voxels under a turned map that leaves voxels of the second turn inside and outside:
+    the samples and the fill out there are the model's."""
+    n, m = LATE_SHAPE, (22, 19, 21)
+    T = _turned(n, m, 25.0, 1.1)
+    late_inside = _inside_from(T, n, m, SECOND_TURN)
+    assert 0 < late_inside < int(np.prod(n)) - SECOND_TURN
+    for dtype in (np.float32, np.float64):
+        moving = _volume(m, 'noise', 32, dtype)
+        for fill in (-7.5, float('nan')):
+            got, want = R.resample(moving, T, n, order=1, fill=fill), M.resample(moving, T, n, order=1, fill=fill)
+            assert got.dtype == np.float64 and got.shape == n
+            assert got.tobytes() == want.tobytes(), (dtype, fill, int((_bits(got) != _bits(want)).sum()))
+        late = got.ravel()[SECOND_TURN:]
+        assert int(np.isnan(late).sum()) == len(late) - late_inside           # the fill shows, and so do samples
+    for dtype in (np.uint8, np.int16, np.float32):
+        moving = (_volume(m, 'noise', 33) * (1.0 if np.dtype(dtype).kind == 'f' else 0.5)).astype(dtype)
+        assert not (moving == dtype(250)).any()                  # a fill that shows
+        got, want = R.resample(moving, T, n, order=0, fill=250), M.resample(moving, T, n, order=0, fill=250)
+        assert _same(got, want), dtype
+        late = got.ravel()[SECOND_TURN:]
+        assert 0 < int((late == dtype(250)).sum()) < len(late)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('n', [(130, 128, 130), (131, 127, 129)], ids=['130x128x130', '131x127x129'])
+def test_shrink_when_the_output_takes_a_second_turn(n):
+    """k_reg_shrink strides over its OUTPUT: (65, 64, 65) = 270 400 and (66, 64, 65) = 274 560 voxels > 262 144.  The odd extents
+    end in a clamped block on every axis."""
+    o = tuple((e + 1) // 2 for e in n)
+    assert int(np.prod(o)) > SECOND_TURN
+    v = _volume(n, 'noise', 34, np.float32)
+    got, want = R.shrink(v), M.shrink(v)
+    assert got.dtype == np.float64 and got.shape == o
+    assert np.array_equal(_bits(got), _bits(want)), int((_bits(got) != _bits(want)).sum())
+    mask = (np.random.default_rng(35).random(n) < 0.1).astype(np.uint8)
+    got, want = R.shrink(mask, mask=True), M.shrink(mask, mask=True)
+    assert got.dtype == np.uint8 and _same(got, want)
+    assert 0 < int(got.ravel()[SECOND_TURN:].sum()) < got.size - SECOND_TURN
 
 
 # ------------------------------------------------------------------ GPU: the loop
