@@ -427,6 +427,13 @@ extern "C" int vmask_reg_hold(int device, const void* host, int64_t bytes, void*
     return VRG_OK;
 }
 
+extern "C" int vmask_reg_fetch(const void* held, void* host, int64_t bytes) {
+    if (!held || !host) { vmask::set_error("null pointer"); return VRG_E_ARG; }
+    if (bytes < 1) { vmask::set_error("registration: a held array has at least one byte"); return VRG_E_ARG; }
+    VMASK_TRY(hipMemcpy(host, held, (size_t)bytes, hipMemcpyDeviceToHost));
+    return VRG_OK;
+}
+
 extern "C" void vmask_reg_release(void* held) {
     DevMem mem;
     if (held) mem.owned.push_back(held);           // freed as the owner leaves scope

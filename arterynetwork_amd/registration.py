@@ -16,6 +16,12 @@ grids and cannot be exchanged with this one without both headers.
 Volumes stay where they are given: tensors on the GPU are used in place and give tensors; host arrays are copied to the device
 by every call of the single entries.  ``register`` (and so ``main``) converts and copies its host arrays once and keeps the
 pyramid and the bin images on the device for its whole search.
+
+Nonlinear registration (``registerNonlinear``, in ``fnirt``'s place) refines what the matrix leaves: a displacement field on the
+fixed grid, a B-spline demons warp by a definition of our own - include/vmask.h ``vmask_warp_*``, DESIGN.md section 9 entry f18.
+Per level of the pyramid one C entry iterates force pass, three-component B-spline fit and update on the device; the pyramid and
+the levels are ``registerNonlinearWith``, host Python over operations that tests/warp_model.py restates in numpy.  A warp is
+float64 ``[3, n0, n1, n2]``: component c is the displacement along axis c of the fixed grid, in fixed voxels.
 """
 from __future__ import annotations
 
@@ -55,6 +61,12 @@ def _lib():
         dll.vmask_reg_hold.argtypes = [i, p, i64, p]
         dll.vmask_reg_release.argtypes = [p]
         dll.vmask_reg_release.restype = None
+        dll.vmask_reg_fetch.argtypes = [p, p, i64]
+        dll.vmask_warp_force.argtypes = [i, p, i, p, i64, i64, i64, p, p, i, i64, i64, i64, p, d, d, d, d, d, p, p, p, p]
+        dll.vmask_warp_fit.argtypes = [i, p, p, i64, i64, i64, p, p]
+        dll.vmask_warp_upsample.argtypes = [i, p, i64, i64, i64, p, i64, i64, i64]
+        dll.vmask_warp_resample.argtypes = [i, p, i, i64, i64, i64, p, p, i, d, p, i64, i64, i64]
+        dll.vmask_warp_field.argtypes = [i, p, i, p, i64, i64, i64, p, i, i64, i64, i64, p, d, d, d, d, p, i, d, d, p, p, p]
     return dll
 
 
@@ -152,6 +164,12 @@ class _Held:
         nbytes = max(1, int(np.prod(self.shape))) * self.dtype.itemsize
         _G._check(_lib().vmask_reg_hold(self.device, None if source is None else source.ctypes.data, nbytes, C.byref(p)))
         self.ptr = p.value
+
+    def numpy(self):
+        out = np.empty(self.shape, self.dtype)
+        if out.size:
+            _G._check(_lib().vmask_reg_fetch(C.c_void_p(self.ptr), out.ctypes.data, out.nbytes))
+        return out
 
     def __del__(self):
         if self.ptr:
@@ -292,36 +310,40 @@ def resample(moving, T, shape, order=1, fill=0, device=0):
     others as float64); order 0 takes the nearest voxel and keeps the type (uint8, int16, int32, float32, float64; bool goes in
     as uint8).  `fill` is written where the voxel falls outside the moving volume."""
     dll = _lib()
-    if order not in (0, 1):
-        raise ValueError('order: 0 or 1')
     shape = tuple(int(x) for x in shape)
     if len(shape) != 3 or min(shape) < 1:
         raise ValueError('shape: three extents')
     t12 = _map12(T)
-    fill = float(fill)
-    if order == 1:
-        v, on_device = _B._volume(moving, (np.float32, np.float64))
-        code, dtype = _code(v, 'tensor' if on_device else 'host'), np.float64
-    else:
-        if _G._on_device(moving):
-            import torch
-            v, on_device = (moving.to(torch.uint8) if moving.dtype == torch.bool else moving).contiguous(), True
-            dtype = np.dtype(str(v.dtype).replace('torch.', ''))
-        else:
-            v, on_device = np.asarray(moving), False
-            v = np.ascontiguousarray(v.astype(np.uint8) if v.dtype == np.bool_ else v)
-            dtype = v.dtype
-        if (v.dim() if on_device else v.ndim) != 3:
-            raise ValueError('expected a 3-D volume')
-        if dtype not in NEAREST_TYPES:
-            raise ValueError('order 0: uint8, int16, int32, float32 or float64')
-        if np.dtype(dtype).kind in 'iu' and not (np.isfinite(fill) and fill == np.floor(fill) and np.iinfo(dtype).min <= fill <= np.iinfo(dtype).max):
-            raise ValueError('fill: a value of the volume\'s type')
-        code = DTYPE_CODES[np.dtype(dtype)]
+    v, on_device, code, dtype, fill = _resample_input(moving, order, fill)
     out = _empty(shape, dtype, v, on_device)
     dev = _B._sync(v, on_device, device)
     _G._check(dll.vmask_reg_resample(dev, _B._ptr(v, on_device), code, *v.shape, t12.ctypes.data, order, fill, _B._ptr(out, on_device), *shape))
     return out
+
+
+def _resample_input(moving, order, fill):
+    """(the volume as ``vmask_reg_resample`` / ``vmask_warp_resample`` take it, on the device?, its dtype code, the output's dtype, fill)"""
+    if order not in (0, 1):
+        raise ValueError('order: 0 or 1')
+    fill = float(fill)
+    if order == 1:
+        v, on_device = _B._volume(moving, (np.float32, np.float64))
+        return v, on_device, _code(v, 'tensor' if on_device else 'host'), np.float64, fill
+    if _G._on_device(moving):
+        import torch
+        v, on_device = (moving.to(torch.uint8) if moving.dtype == torch.bool else moving).contiguous(), True
+        dtype = np.dtype(str(v.dtype).replace('torch.', ''))
+    else:
+        v, on_device = np.asarray(moving), False
+        v = np.ascontiguousarray(v.astype(np.uint8) if v.dtype == np.bool_ else v)
+        dtype = v.dtype
+    if (v.dim() if on_device else v.ndim) != 3:
+        raise ValueError('expected a 3-D volume')
+    if dtype not in NEAREST_TYPES:
+        raise ValueError('order 0: uint8, int16, int32, float32 or float64')
+    if np.dtype(dtype).kind in 'iu' and not (np.isfinite(fill) and fill == np.floor(fill) and np.iinfo(dtype).min <= fill <= np.iinfo(dtype).max):
+        raise ValueError('fill: a value of the volume\'s type')
+    return v, on_device, DTYPE_CODES[np.dtype(dtype)], dtype, fill
 
 
 # ------------------------------------------------------------------ host: the search
@@ -528,6 +550,275 @@ def applyTransform(baseFolder, volumeName, matrixName, referenceName=BRAIN_FILE,
         volume = volume.astype(widen.get(volume.dtype, volume.dtype))
     result = resample(volume, (W, rA, vA), reference.shape, order=order, fill=0)
     outputName = outputName or _stem(volumeName) + 'Transformed.nii.gz'
+    path = os.path.join(baseFolder, outputName)
+    saveVolume(result, rA, path, astype=result.dtype if order == 0 else np.float32)
+    print('{} saved to {}.'.format(outputName, path))
+    return result
+
+
+# ------------------------------------------------------------------ nonlinear: the device entries
+def _take_warp(u, grid=None, name='warp'):
+    """(a float64 [3, n0, n1, n2] array as the library takes it, its address, 'held' / 'tensor' / 'host')"""
+    if isinstance(u, _Held):
+        shape, a, ptr, kind = u.shape, u, u.ptr, 'held'
+        if u.dtype != np.float64:
+            raise ValueError('{}: float64'.format(name))
+    elif _G._on_device(u):
+        import torch
+        a = u.to(torch.float64).contiguous()
+        shape, ptr, kind = tuple(a.shape), a.data_ptr(), 'tensor'
+    else:
+        a = np.ascontiguousarray(np.asarray(u), dtype=np.float64)
+        shape, ptr, kind = a.shape, a.ctypes.data, 'host'
+    if len(shape) != 4 or shape[0] != 3 or (grid is not None and tuple(shape[1:]) != tuple(int(x) for x in grid)):
+        raise ValueError('{}: float64 [3, n0, n1, n2] on the fixed grid'.format(name))
+    return a, ptr, kind
+
+
+def _finite(x, name):
+    x = float(x)
+    if not np.isfinite(x):
+        raise ValueError('{}: finite'.format(name))
+    return x
+
+
+def _force_args(fixed, moving, T, flo, fs, mlo, ms, maxStep, mask):
+    f, fptr, fkind = _take(fixed)
+    g, gptr, gkind = _take(moving)
+    m, mptr = _take_mask(mask, f, fkind)
+    scales = [_finite(x, name) for x, name in ((flo, 'flo'), (fs, 'fs'), (mlo, 'mlo'), (ms, 'ms'))]
+    return (f, fptr, fkind), (g, gptr, gkind), (m, mptr), _map12(T), scales, _B._positive(maxStep, 'maxStep')
+
+
+def forcePass(fixed, moving, T, warp, flo, fs, mlo, ms, maxStep=0.5, mask=None, device=0):
+    """``vmask_warp_force``: (delta float64 [3, n0, n1, n2], part uint8 [n0, n1, n2], S, count) - the demons force at every voxel of
+    the fixed grid that takes part (inside `mask`, finite, its sample of `moving` through `T` and `warp` inside), which those
+    are, and the sum of their squared residuals and their number.  fs and ms are ``binScale(lo, hi, 1)`` of the two volumes."""
+    dll = _lib()
+    (f, fptr, fkind), (g, gptr, gkind), (m, mptr), t12, scales, maxStep = _force_args(fixed, moving, T, flo, fs, mlo, ms, maxStep, mask)
+    u, uptr, ukind = _take_warp(warp, f.shape)
+    delta, dptr = _make((3,) + tuple(f.shape), np.float64, f, fkind)
+    part, pptr = _make(f.shape, np.uint8, f, fkind)
+    S, count = C.c_double(0.0), C.c_int64(0)
+    dev = _device(g, gkind, _device(f, fkind, device))
+    if ukind == 'tensor':
+        _B._sync(u, True, device)
+    _G._check(dll.vmask_warp_force(dev, fptr, _code(f, fkind), mptr, *f.shape, uptr, gptr, _code(g, gkind), *g.shape, t12.ctypes.data, *scales, maxStep,
+                                   dptr, pptr, C.addressof(S), C.addressof(count)))
+    return delta, part, S.value, count.value
+
+
+def fitForces(delta, part, spans, device=0):
+    """``vmask_warp_fit``: float64 [3, spans + 3 per axis], ``bias.bsplineFit(delta[c], part, spans)`` for the three components."""
+    dll = _lib()
+    M = _B._spans(spans, 64, 'spans')
+    d, dptr, kind = _take_warp(delta, None, 'delta')
+    p, pptr, _ = _take(part, True)
+    if tuple(p.shape) != tuple(d.shape[1:]):
+        raise ValueError('part: the shape of a component of delta')
+    phi, optr = _make([3] + [int(k) + 3 for k in M], np.float64, d, kind)
+    _G._check(dll.vmask_warp_fit(_device(d, kind, device), dptr, pptr, *p.shape, M.ctypes.data, optr))
+    return phi
+
+
+def upsampleWarp(coarse, shape, device=0):
+    """``vmask_warp_upsample``: the warp of a coarser level of the pyramid on the grid of `shape`, in that grid's voxels."""
+    dll = _lib()
+    shape = tuple(int(x) for x in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError('shape: three extents')
+    c, cptr, kind = _take_warp(coarse)
+    fine, fptr = _make((3,) + shape, np.float64, c, kind)
+    _G._check(dll.vmask_warp_upsample(_device(c, kind, device), cptr, *c.shape[1:], fptr, *shape))
+    return fine
+
+
+def warpLevel(fixed, moving, T, warp, flo, fs, mlo, ms, spans, iterations=30, maxStep=0.5, convergenceThreshold=0.01, mask=None, device=0):
+    """``vmask_warp_field``: the iterations of one level from `warp`.  Returns (the warp, one row (cost, count, max |dphi|) per
+    iteration).  A warp on the device (a tensor, a held array) is updated in place; a host array is copied first.  ValueError
+    when no voxel takes part at the first iteration."""
+    from ._capi import VrgError
+    dll = _lib()
+    (f, fptr, fkind), (g, gptr, gkind), (m, mptr), t12, scales, maxStep = _force_args(fixed, moving, T, flo, fs, mlo, ms, maxStep, mask)
+    M = _B._spans(spans, 64, 'spans')
+    iterations, threshold = int(iterations), _B._positive(convergenceThreshold, 'convergenceThreshold')
+    if iterations < 1 or iterations > 200:
+        raise ValueError('iterations: 1 to 200')
+    u, uptr, ukind = _take_warp(np.array(warp, dtype=np.float64) if isinstance(warp, np.ndarray) else warp, f.shape)
+    rows = np.zeros((iterations, 3), np.float64)
+    count = C.c_int64(0)
+    dev = _device(g, gkind, _device(f, fkind, device))
+    if ukind == 'tensor':
+        _B._sync(u, True, device)
+    try:
+        _G._check(dll.vmask_warp_field(dev, fptr, _code(f, fkind), mptr, *f.shape, gptr, _code(g, gkind), *g.shape, t12.ctypes.data, *scales, M.ctypes.data,
+                                       iterations, maxStep, threshold, uptr, rows.ctypes.data, C.addressof(count)))
+    except VrgError as e:
+        if e.code == -1:                                     # (what the host can check has passed: no voxel takes part)
+            raise ValueError(str(e))
+        raise
+    return u, rows[:count.value].copy()
+
+
+def warpResample(moving, W, warp, fixedAffine=None, movingAffine=None, order=1, fill=0, device=0):
+    """``vmask_warp_resample``: `moving` on the fixed grid - the grid of `warp`, float64 [3, n0, n1, n2] - through the matrix `W`
+    that ``register`` returns (None: the identity), the two voxel -> world affines and the warp that ``registerNonlinear`` returns.
+    order, fill and the types as ``resample``; a zero warp gives ``resample``'s bytes.  A tensor on the GPU gives a tensor."""
+    dll = _lib()
+    t12 = _map12((np.eye(4) if W is None else W, fixedAffine, movingAffine))
+    v, on_device, code, dtype, fill = _resample_input(moving, order, fill)
+    if on_device and not _G._on_device(warp) and not isinstance(warp, _Held):
+        import torch
+        warp = torch.as_tensor(np.asarray(warp, dtype=np.float64), device=v.device)
+    u, uptr, ukind = _take_warp(warp)
+    shape = tuple(int(x) for x in u.shape[1:])
+    out = _empty(shape, dtype, v, on_device)
+    dev = _B._sync(v, on_device, device)
+    if ukind == 'tensor':
+        _B._sync(u, True, device)
+    _G._check(dll.vmask_warp_resample(dev, _B._ptr(v, on_device), code, *v.shape, t12.ctypes.data, uptr, order, fill, _B._ptr(out, on_device), *shape))
+    return out
+
+
+# ------------------------------------------------------------------ nonlinear: the levels
+def registerNonlinearWith(ops, fixed, moving, W=None, fixedAffine=None, movingAffine=None, fixedMask=None, splineSpans=(2, 2, 2), levels=3,
+                          iterations=30, maxStep=0.5, convergenceThreshold=0.01):
+    """``registerNonlinear`` over the operations of `ops`: ``extrema(volume, mask)``, ``shrink(array, mask)``, ``zeros(like)`` (a
+    zero warp on the grid of a volume), ``upsample(warp, shape)``, ``level(fixed, moving, T, warp, flo, fs, mlo, ms, spans,
+    iterations, maxStep, threshold, mask)`` (the iterations of one level: the warp and one row (cost, count, max |dphi|) per
+    iteration) and ``result(warp)``; an optional ``hold(array)`` may move an array to where the operations want it.  The library
+    passes its GPU entries, the tests' model (tests/warp_model.py) its numpy restatements; the conversion of the volumes, the
+    pyramid, the maps and scales of the levels and the trace are this function for both."""
+    m0 = _B._spans(splineSpans, 64, 'splineSpans')
+    levels, iterations = int(levels), int(iterations)
+    if levels < 1 or levels > 8:
+        raise ValueError('levels: 1 to 8')
+    if iterations < 1 or iterations > 200:
+        raise ValueError('iterations: 1 to 200')
+    maxStep, threshold = _B._positive(maxStep, 'maxStep'), _B._positive(convergenceThreshold, 'convergenceThreshold')
+    W = _affine(W, 'W')
+    fA, mA = _affine(fixedAffine, 'fixedAffine'), _affine(movingAffine, 'movingAffine')
+    if len(fixed.shape) != 3 or len(moving.shape) != 3:
+        raise ValueError('expected 3-D volumes')
+    if fixedMask is not None and tuple(fixedMask.shape) != tuple(fixed.shape):
+        raise ValueError('fixedMask: the shape of the fixed volume')
+    fixed, on_device = _B._volume(fixed, (np.float32, np.float64))
+    moving = _B._volume(moving, (np.float32, np.float64))[0]
+    if fixedMask is not None:
+        fixedMask = _B._mask(fixedMask, fixed, on_device)
+    hold = getattr(ops, 'hold', lambda a: a)
+    fixed, moving, fixedMask = hold(fixed), hold(moving), None if fixedMask is None else hold(fixedMask)
+    # the pyramid of registerWith: index 0 is the full resolution
+    F, M = [(fixed, fA, fixedMask)], [(moving, mA)]
+    for _ in range(levels - 1):
+        (f, a, m), (g, b) = F[-1], M[-1]
+        if min((int(n) + 1) // 2 for n in tuple(f.shape) + tuple(g.shape)) < 8:
+            break
+        F.append((ops.shrink(f, False), a @ SHRINK, None if m is None else ops.shrink(m, True)))
+        M.append((ops.shrink(g, False), b @ SHRINK))
+    F.reverse()
+    M.reverse()
+    warp, rows = None, []
+    for level, ((f, a, m), (g, b)) in enumerate(zip(F, M)):
+        spans = [min(64, int(k) * 2 ** level) for k in m0]
+        flo, fhi = ops.extrema(f, None)                      # (of the whole volumes: the mask limits the forces, not the scaling)
+        mlo, mhi = ops.extrema(g, None)
+        fs, ms = binScale(flo, fhi, 1), binScale(mlo, mhi, 1)
+        T = voxelMap(W, a, b)
+        warp = ops.zeros(f) if warp is None else ops.upsample(warp, tuple(int(n) for n in f.shape))
+        warp, r = ops.level(f, g, T, warp, flo, fs, mlo, ms, spans, iterations, maxStep, threshold, m)
+        rows.extend((float(level), float(c), float(n), float(top)) for c, n, top in r)
+    return ops.result(warp), np.array(rows, dtype=np.float64).reshape(len(rows), 4)
+
+
+def registerNonlinear(fixed, moving, W=None, fixedAffine=None, movingAffine=None, fixedMask=None, splineSpans=(2, 2, 2), levels=3, iterations=30,
+                      maxStep=0.5, convergenceThreshold=0.01, device=0):
+    """The warp that brings `moving` onto `fixed` where the matrix `W` of ``register`` (None: the identity) leaves a smooth
+    deformation, and the trace: (warp, trace).
+
+    warp is float64 [3, n0, n1, n2]: at fixed voxel v the moving volume is sampled at T (v + warp[:, v]), T = ``voxelMap(W,
+    fixedAffine, movingAffine)`` - displacements in fixed voxels (``warpResample`` applies it).  `levels` block-mean pyramid levels
+    run coarse to fine (fewer when an extent would fall below 8), the warp doubled and resampled in between; at level L the update
+    lives on a cubic B-spline lattice of `splineSpans` 2^L spans per axis (at most 64).  Per iteration, at most `iterations` a level:
+    the demons force of the squared difference of the two volumes, each scaled to [0, 1] between its extrema (over `fixedMask` for
+    the fixed one) - no single force exceeds `maxStep` voxels -, its B-spline fit over the voxels that take part, and the fit's
+    evaluation added to the warp.  A level ends when the largest control-point update falls below `convergenceThreshold` (voxels of
+    that level).  trace: one row (level, cost before the step, voxels that took part, max |update|) per iteration.  ValueError when
+    no voxel takes part at a level's first iteration (an empty mask, volumes that do not overlap).  The cost is a sum of squared
+    differences: both volumes must be of one modality.  Volumes of any dtype are taken (float32 and float64 as they are, others
+    as float64); host arrays are copied to the device once and give a host array; tensors on the GPU are used in place and give a
+    tensor."""
+    def zeros(f):
+        if isinstance(f, _Held):
+            return _Held((3,) + f.shape, np.float64, np.zeros((3,) + f.shape), f.device)
+        import torch
+        return torch.zeros((3,) + tuple(f.shape), dtype=torch.float64, device=f.device)
+    ops = types.SimpleNamespace(extrema=lambda v, m: extrema(v, m, device), shrink=lambda v, m: shrink(v, m, device), zeros=zeros,
+                                upsample=lambda u, shape: upsampleWarp(u, shape, device),
+                                level=lambda f, g, T, u, flo, fs, mlo, ms, spans, it, step, thr, m: warpLevel(f, g, T, u, flo, fs, mlo, ms, spans, it, step, thr, m, device),
+                                result=lambda u: u.numpy() if isinstance(u, _Held) else u,
+                                hold=lambda a: a if _G._on_device(a) else _Held(a.shape, a.dtype, a, device))
+    _lib()
+    return registerNonlinearWith(ops, fixed, moving, W, fixedAffine, movingAffine, fixedMask, splineSpans, levels, iterations, maxStep, convergenceThreshold)
+
+
+# ------------------------------------------------------------------ nonlinear: the files
+def mainNonlinear(baseFolder=None, movingName=None, fixedName=BRAIN_FILE, matrixName=None, outputName=None, warpName=None, **parameters):
+    """File-level step after ``main``: `movingName` warped onto `fixedName` (both in `baseFolder`).  The matrix W is read from
+    `<moving>ToFixed.mat` (`matrixName`) where ``main`` has left one; where not, ``register`` runs first with its defaults and the
+    matrix is written there.  Then ``registerNonlinear(W=W, **parameters)`` with the files' affines.  Writes
+    `<moving>Warped.nii.gz` (`outputName`): the moving volume through W and the warp on the fixed grid, trilinear, float32, the
+    fixed file's affine; and `<moving>Warp.nii.gz` (`warpName`): the warp as a 4-D float32 volume [n0, n1, n2, 3] with that
+    affine, displacements in fixed voxels.  Returns (warp, the warped volume), both float64."""
+    if baseFolder is None:
+        baseFolder = os.getcwd()
+    if movingName is None:
+        raise ValueError('movingName: the file to register')
+    if 'fixedAffine' in parameters or 'movingAffine' in parameters or 'W' in parameters:
+        raise ValueError('mainNonlinear takes the affines and the matrix from the files')
+    device = parameters.get('device', 0)
+    fixed, fA = loadVolume(baseFolder, fixedName)
+    moving, mA = loadVolume(baseFolder, movingName)
+    fixed, moving = np.ascontiguousarray(fixed), np.ascontiguousarray(moving)
+    matrixName = matrixName or _stem(movingName) + 'ToFixed.mat'
+    path = os.path.join(baseFolder, matrixName)
+    if os.path.exists(path):
+        W = np.loadtxt(path).reshape(4, 4)
+    else:
+        W, _ = register(fixed, moving, fixedAffine=fA, movingAffine=mA, device=device)
+        np.savetxt(path, W, fmt='%.17g')
+        print('{} saved to {}.'.format(matrixName, path))
+    warp, _ = registerNonlinear(fixed, moving, W=W, fixedAffine=fA, movingAffine=mA, **parameters)
+    result = warpResample(moving, W, warp, fA, mA, order=1, fill=0, device=device)
+    outputName = outputName or _stem(movingName) + 'Warped.nii.gz'
+    path = os.path.join(baseFolder, outputName)
+    saveVolume(result, fA, path, astype=np.float32)
+    print('{} saved to {}.'.format(outputName, path))
+    warpName = warpName or _stem(movingName) + 'Warp.nii.gz'
+    path = os.path.join(baseFolder, warpName)
+    saveVolume(np.moveaxis(warp, 0, 3), fA, path, astype=np.float32)
+    print('{} saved to {}.'.format(warpName, path))
+    return warp, result
+
+
+def applyWarp(baseFolder, volumeName, matrixName, warpName, referenceName=BRAIN_FILE, order=0, outputName=None, device=0):
+    """Carry a mask or another series of the moving image's space over the matrix and the warp that ``mainNonlinear`` wrote:
+    `volumeName` resampled onto the grid of `referenceName` through W of `matrixName` and the (float32) warp of `warpName`,
+    nearest voxel and the file's type by default (int8 and uint16 widen to int16 and int32), trilinear float32 with order=1;
+    written as `<volume>Warped.nii.gz` (`outputName`) with the reference's affine.  Returns the volume."""
+    volume, vA = loadVolume(baseFolder, volumeName)
+    reference, rA = loadVolume(baseFolder, referenceName)
+    stored, _ = loadVolume(baseFolder, warpName)
+    if stored.ndim != 4 or stored.shape[3] != 3 or stored.shape[:3] != reference.shape:
+        raise ValueError('{}: a 4-D warp [n0, n1, n2, 3] on the grid of {}'.format(warpName, referenceName))
+    warp = np.ascontiguousarray(np.moveaxis(stored, 3, 0), dtype=np.float64)
+    W = np.loadtxt(os.path.join(baseFolder, matrixName)).reshape(4, 4)
+    volume = np.ascontiguousarray(volume)
+    if order == 0:
+        widen = {np.dtype(np.int8): np.int16, np.dtype(np.uint16): np.int32, np.dtype(np.bool_): np.uint8}
+        volume = volume.astype(widen.get(volume.dtype, volume.dtype))
+    result = warpResample(volume, W, warp, rA, vA, order=order, fill=0, device=device)
+    outputName = outputName or _stem(volumeName) + 'Warped.nii.gz'
     path = os.path.join(baseFolder, outputName)
     saveVolume(result, rA, path, astype=result.dtype if order == 0 else np.float32)
     print('{} saved to {}.'.format(outputName, path))

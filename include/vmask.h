@@ -91,6 +91,13 @@
  *                      numpy restatement tests/registration_model.py; the corratio cost bit-equal to its restatement, mi and nmi
  *                      within a measured distance (the host's log); bit-identical repeats.  Not claimed: agreement with flirt
  *                      (its smoothing, partial-volume weights, optimiser and matrix convention all differ).
+ *   vmask_warp_*       the nonlinear part of the same step, which the README leaves to FSL fnirt: a displacement field on the fixed
+ *                      grid refined by demons forces (sum of squared differences after a linear intensity scaling) that a
+ *                      multilevel cubic B-spline fit smooths, the fit and the evaluation those of vmask_bias_*, the sample that of
+ *                      vmask_reg_*; DESIGN.md section 9, f18.  Claimed: bit equality of the force pass, the three-numerator fit,
+ *                      the upsampled and the final warp, the trace and the resampled volumes with the numpy restatement
+ *                      tests/warp_model.py; a measured recovery of a known deformation; bit-identical repeats.  Not claimed:
+ *                      agreement with fnirt, cross-modality costs, a diffeomorphic or invertible warp.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -586,9 +593,78 @@ int vmask_reg_resample(int device, const void* moving, int dtype, int64_t m0, in
 /* A device array that outlives a call: registration.register keeps the volumes, the pyramid and the bin images of host arrays on
  * the device through it, so that they cross once and not with every evaluation.  *held receives `bytes` bytes of device memory,
  * filled from `host` where that is not NULL; vmask_reg_release frees them (NULL is allowed).  VRG_E_ARG: bytes < 1, held NULL;
- * VRG_E_NOGPU; VRG_E_MEM. */
+ * VRG_E_NOGPU; VRG_E_MEM.  vmask_reg_fetch copies the first `bytes` bytes of a held array to the host (VRG_E_ARG: a null pointer,
+ * bytes < 1): how the warp of registration.registerNonlinear comes back. */
 int vmask_reg_hold(int device, const void* host /* may be NULL */, int64_t bytes, void** held);
+int vmask_reg_fetch(const void* held, void* host, int64_t bytes);
 void vmask_reg_release(void* held);
+
+/* Nonlinear registration by a B-spline demons warp, by a definition of our own (no parity with FSL fnirt is claimed).  All arithmetic
+ * is float64, EVERY OPERATION ONE IEEE DOUBLE OPERATION IN THE WRITTEN ASSOCIATION, nothing contracted into an FMA; no float atomics.
+ * Volumes are C-contiguous (i0, i1, i2); n are the fixed extents, m the moving ones, V = n0 n1 n2.
+ *
+ * Warp.  u: float64 [3][n0][n1][n2] on the fixed grid, component c the displacement along axis c in fixed-voxel units.  T: 12 doubles
+ * on the host, the fixed voxel -> moving voxel map of vmask_reg_*.  At fixed voxel v = (i0, i1, i2):
+ *     q_c = (double) v_c + u_c[v];      p_a = ((T[a][0]*q_0 + T[a][1]*q_1) + T[a][2]*q_2) + T[a][3].
+ * The inside test (0 <= p_a <= m_a - 1; false for a NaN), f_a = floor(p_a), t_a = p_a - f_a, the upper neighbour min(f_a + 1, m_a - 1)
+ * and the interpolation along axis 2, then 1, then 0, each step lo + t * (hi - lo), are those of vmask_reg_joint_hist:
+ *     x[a][b] = v[a][b][0] + t_2 * (v[a][b][1] - v[a][b][0]);  y[a] = x[a][0] + t_1 * (x[a][1] - x[a][0]);  m = y[0] + t_0 * (y[1] - y[0]).
+ * A sample that is not finite counts as outside.  With u = 0, q_c = (double) v_c and every sample is that of vmask_reg_*.
+ *
+ * Force pass.  A voxel TAKES PART iff mask[v] != 0 (mask uint8, may be NULL: every voxel), (double) F[v] is finite and its sample m is
+ * inside.  For such a voxel, with the caller's flo, fs, mlo, ms (fs = 1 / (fhi - flo), 0 when fhi == flo; ms likewise) and maxStep:
+ *     r = (F - flo) * fs - (m - mlo) * ms;
+ *     g0 = y[1] - y[0];   e[a] = x[a][1] - x[a][0],  g1 = e[0] + t_0 * (e[1] - e[0]);
+ *     d[a][b] = v[a][b][1] - v[a][b][0],  h[a] = d[a][0] + t_1 * (d[a][1] - d[a][0]),  g2 = h[0] + t_0 * (h[1] - h[0]);
+ *     G_c = ((g0*T[0][c] + g1*T[1][c]) + g2*T[2][c]) * ms;
+ *     a2 = 1.0 / ((4.0*maxStep)*maxStep);    den = ((G_0*G_0 + G_1*G_1) + G_2*G_2) + (r*r)*a2;
+ *     delta_c = (r*G_c) / den  where den > 0 and den is finite, else 0.0 (the voxel still takes part).
+ * |delta| <= maxStep (Thirion's bound: |r||G| <= (|G|^2 + r^2 a2) maxStep).  A voxel that takes no part has delta = 0 and part = 0.
+ *     S = sum over i2 ( sum over i1 ( sum over i0 of r*r ) ) over the voxels that take part, every sum ascending from +0.0 (the last,
+ *     n2-long one on the host); count: their number, a 64-bit integer; the cost of u is S / (double) count.
+ * delta: float64 [3][n0][n1][n2]; part: uint8 [n0][n1][n2], 0 / 1; S, count: host pointers.
+ * VRG_E_ARG, before a device is looked for and before anything is written: a null pointer (mask excepted); a dtype of either volume
+ * other than VRG_F32 / VRG_F64; a T, flo, fs, mlo or ms that is not finite; maxStep not finite and positive (or so small that a2 is not
+ * finite); a fixed or moving shape
+ * outside the envelope of the other passes.  VRG_E_MEM: the arrays that are host arrays do not fit the device; everything is freed. */
+int vmask_warp_force(int device, const void* fixed, int fdtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
+                     const double* u, const void* moving, int mdtype, int64_t m0, int64_t m1, int64_t m2, const double* T /* 12, host */,
+                     double flo, double fs, double mlo, double ms, double maxStep, double* delta, uint8_t* part, double* S /* host */,
+                     int64_t* count /* host */);
+
+/* The fit of the three force components over the voxels with part != 0: phi[c] = vmask_bias_fit(delta[c], part, spans) for c = 0, 1, 2,
+ * bit for bit - the denominators do not depend on c and are computed once.  phi: float64 [3][M_0 + 3][M_1 + 3][M_2 + 3].
+ * VRG_E_ARG: spans outside 1..64, a null pointer, a shape outside the envelope.  VRG_E_MEM: delta and part where they are host arrays
+ * and 4 (M_0 + 3) n1 n2 doubles do not fit the device. */
+int vmask_warp_fit(int device, const double* delta, const uint8_t* part, int64_t n0, int64_t n1, int64_t n2, const int* spans, double* phi);
+
+/* The warp of the next finer level of the pyramid of vmask_reg_shrink (coarse extents c, usually ceil(n / 2)):
+ *     fine[comp][i] = 2.0 * trilinear(coarse[comp]) at x_a = clamp(((double) i_a - 0.5) * 0.5, 0, c_a - 1),
+ * f_a = floor(x_a), t_a = x_a - f_a, upper neighbour min(f_a + 1, c_a - 1), interpolation along axis 2, 1, 0 in the form above.
+ * coarse: float64 [3][c0][c1][c2]; fine: float64 [3][n0][n1][n2].  VRG_E_ARG: a null pointer, a shape outside the envelope. */
+int vmask_warp_upsample(int device, const double* coarse, int64_t c0, int64_t c1, int64_t c2, double* fine, int64_t n0, int64_t n1, int64_t n2);
+
+/* The moving volume on the fixed grid through T and the warp u (float64 [3][n0][n1][n2]): vmask_reg_resample with p of the warp above.
+ * order 1: float64 samples (dtype VRG_F32 or VRG_F64); order 0: the voxel at floor(p_a + 0.5) in the moving volume's own type
+ * (VRG_U8, VRG_I16, VRG_I32, VRG_F32, VRG_F64).  fill where the voxel is outside.  u = 0 gives the bytes of vmask_reg_resample.
+ * Errors as vmask_reg_resample, and a null u. */
+int vmask_warp_resample(int device, const void* moving, int dtype, int64_t m0, int64_t m1, int64_t m2, const double* T /* 12, host */,
+                        const double* u, int order, double fill, void* out, int64_t n0, int64_t n1, int64_t n2);
+
+/* The loop of one level.  u (float64 [3][n0][n1][n2]) is the start and receives the result.  Per iteration, at most `iterations`:
+ *   1. the force pass at u: delta, part, S, count.  count == 0 at the first iteration refuses the call (VRG_E_ARG, u unchanged).
+ *   2. dphi = vmask_warp_fit(delta, part, spans);  u_c <- u_c + vmask_bias_eval(dphi_c) over the whole grid.
+ *   3. dphi goes to the host; top = max |dphi| over the three lattices (a NaN is skipped); top < threshold ends the level.
+ * trace (host, may be NULL): one record of three doubles per iteration - S / (double) count (the cost BEFORE the step), (double)
+ * count, top -, room for `iterations` records; ntrace (host, may be NULL): their number.  The pyramid, T and the scales of every
+ * level and the warp between levels are the caller's (registration.registerNonlinearWith).
+ * VRG_E_ARG, before a device is looked for: as vmask_warp_force, and spans outside 1..64, iterations outside 1..200, a threshold that
+ * is not finite and positive.  VRG_E_MEM: the arrays that are host arrays, three float64 force volumes, the participation bytes and
+ * 4 (M_0 + 3) n1 n2 doubles of the fit do not fit the device (volumes are not processed in slabs); everything allocated is freed. */
+int vmask_warp_field(int device, const void* fixed, int fdtype, const uint8_t* mask /* may be NULL */, int64_t n0, int64_t n1, int64_t n2,
+                     const void* moving, int mdtype, int64_t m0, int64_t m1, int64_t m2, const double* T /* 12, host */, double flo, double fs,
+                     double mlo, double ms, const int* spans, int iterations, double maxStep, double threshold, double* u,
+                     double* trace /* may be NULL */, int64_t* ntrace /* may be NULL */);
 
 /* Skull stripping: the brain mask of a head volume, by a definition of our own (the reference leaves the step to an atlas-based GUI
  * plugin; no parity with it is claimed).  Atlas-free, after the Brain Surface Extractor recipe: Marr-Hildreth edges, erosion, the
