@@ -13,10 +13,12 @@ from .skeletonization import branchTerritories, territoryVolumes, geodesicTerrit
 from .skeletonization import branchMorphometry, BranchMorphometry, deriveMorphometry, pathLengths, writeMorphometry  # noqa: F401
 from .skeletonization import partitionCompartments, Compartments, compartmentTerritories, compartmentSummary, writeCompartments  # noqa: F401
 from .geodesic import geodesicDistance  # noqa: F401
+from .reconnect import bridgeCandidates, selectBridges, applyBridges, vesselCost, tipRegions, Bridges  # noqa: F401  (reconnect.reconnect keeps the module's name free)
 from .flow import simulateFlow, FlowResult, branchResistance, terminalPressures, referenceResiduals  # noqa: F401
 
 __all__ = ['variationalRegionGrowing', 'vesselnessFilter', 'sigmasFromDiameters', 'anisotropicDiffusion', 'medianFilter', 'biasFieldCorrection', 'logBiasField', 'register', 'resample', 'brainExtraction',
            'branchTerritories', 'territoryVolumes',
            'geodesicTerritories', 'geodesicDistance', 'branchMorphometry', 'BranchMorphometry', 'deriveMorphometry', 'pathLengths', 'writeMorphometry',
            'partitionCompartments', 'Compartments', 'compartmentTerritories', 'compartmentSummary', 'writeCompartments',
+           'bridgeCandidates', 'selectBridges', 'applyBridges', 'vesselCost', 'tipRegions', 'Bridges',
            'simulateFlow', 'FlowResult', 'branchResistance', 'terminalPressures', 'referenceResiduals']

@@ -98,6 +98,14 @@
  *                      the upsampled and the final warp, the trace and the resampled volumes with the numpy restatement
  *                      tests/warp_model.py; a measured recovery of a known deformation; bit-identical repeats.  Not claimed:
  *                      agreement with fnirt, cross-modality costs, a diffeomorphic or invertible warp.
+ *   vmask_bridge       the "Reconnect" operation of the reference's manual-correction GUI (manualCorrectionGUIDetail.py:739-951, Usage
+ *                      step 5), which joins two branches across a gap along a spline that the user anchors by four clicks; here,
+ *                      with no GUI: for every two components of the vessel mask the cheapest path between them through a cost
+ *                      volume (derived from vesselness), within a bound on the cost; DESIGN.md section 9, f19.  Claimed: exact
+ *                      equality - the bits of dist, root, pred, costs, every integer - with the Jacobi model
+ *                      tests/bridge_model.py, which a heap Dijkstra beside it confirms; bit-identical repeats.  Not claimed: the
+ *                      reference's spline geometry, its Grow and Cut, sub-voxel paths, bridges inside one component; which
+ *                      bridges to take is the Python layer's decision (reconnect.selectBridges).
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -751,6 +759,49 @@ int vmask_fill_holes(int device, const uint8_t* mask, int64_t n0, int64_t n1, in
 int vmask_brain_extract(int device, const void* volume, int dtype, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
                         double sigma, double threshold, double floor, int erosion, int closing, int64_t seed /* or -1 */, uint8_t* out,
                         uint8_t* stages /* may be NULL */, int64_t* info /* 16, may be NULL */);
+
+/* Minimal-cost bridges between the components of a mask.  idx = C-order linear index.
+ * mask (uint8): the vessel mask; its 26-connected components are numbered 1..n as vmask_label numbers them.
+ * domain (uint8, may be NULL: the whole volume): where a path may run; effective domain = domain != 0 or mask != 0.
+ * cost (VRG_F32 or VRG_F64, used as float64): c(v) > 0, read inside the effective domain only.
+ * tips (uint8, may be NULL: all 1): the mask voxels that count as vessel ends.   spacing = (h0, h1, h2), NULL: 1 1 1.
+ * Weights: the 26 offsets have codes k = 0..25, the lexicographic order of (d0, d1, d2) in -1..1 with the centre left out (the
+ * opposite of k is 25 - k).  hw[k] = 0.5 sqrt((d0 h0)^2 + (d1 h1)^2 + (d2 h2)^2): computed once on the host in float64, the squares
+ * summed in the order of the axes, the halving exact.  w(u, v) = fl(fl(c(u) + c(v)) hw[k]) for v = u + offset k: symmetric.  No
+ * operation below is fused: every sum is fl(D + w) with w already rounded.
+ * Flood: R = 0.5 max_cost.  Every mask voxel is a source: D = 0, Root = its own idx.  A domain voxel outside the mask has
+ * D(v) = min over its domain neighbours u of fl(D(u) + w(u, v)) if that is <= R, else +inf - the least fixed point, what Dijkstra
+ * computes with the same additions.  No path passes through a mask voxel: it is a source itself.
+ * Root(v) = the smallest Root(u) among the tight predecessors u, fl(D(u) + w(u, v)) == D(v).  Pred(v) = the code k of the tight
+ * predecessor u = v + offset k with Root(u) == Root(v) of smallest k.  Both are unique fixed points (w > 0, so D(u) < D(v));
+ * following Pred from v ends at the mask voxel Root(v).
+ * Contact: an ordered pair (u, v = u + offset k) of voxels with finite D such that a = comp(Root(u)) < b = comp(Root(v)) and at
+ * least tip_rule (0, 1 or 2) of Root(u), Root(v) have tips != 0.  Its cost K = fl(fl(D(u) + D(v)) + w(u, v)).
+ * Bridge of a pair (a, b): its contact of smallest (K, idx(u), k), kept iff K <= max_cost.  Its path: the Pred chain of u
+ * reversed, then the Pred chain of v - mask voxel of a .. u, v .. mask voxel of b, both mask voxels included, consecutive entries
+ * 26-adjacent.
+ * Outputs, the bridges ascending by (a, b): pairs (cap_pair x 6 int64: a, b, idx(u), idx(v), Root(u), Root(v)), costs (cap_pair
+ * float64: K), offsets (cap_pair + 1) and voxels (cap_vox): path i = voxels[offsets[i] .. offsets[i + 1]).  All four NULL: counts
+ * only.  Otherwise all four are given; too small a capacity: VRG_E_ARG with the needed sizes in counts, nothing else written.
+ * Dense outputs, each may be NULL: dist (float64: 0 in the mask, -1 outside the domain, +inf unreached), root (int32: -1 where
+ * there is none), pred (uint8: the code k, 255 where there is none), comp (int32: the component labels, 0 outside the mask).
+ * counts (int64, 10, may be NULL): [0] components, [1] domain voxels, [2] reached voxels outside the mask, [3] qualifying
+ * contacts, [4] pairs with a contact, [5] bridges kept, [6] path entries (= offsets[counts[5]]), [7] 8x8x8 bricks with storage,
+ * [8] flood rounds, [9] root rounds.  [7..9] describe the run, not the result; everything else is a pure function of the
+ * inputs and bit-identical between runs.
+ * VRG_E_ARG, counted on the device before anything is written: a cost inside the effective domain that is not finite or not > 0;
+ * max_cost not finite or not > 0; R / w_min > 2^40 with w_min = fl(fl(2 c_min) min hw), c_min the smallest cost in the domain
+ * (the bound keeps fl(D + w) > D); a spacing that is not finite and positive, or with max / min > 1000; tip_rule outside 0..2; a
+ * dtype other than the two; a shape outside the envelope of the other passes.
+ * VRG_E_MEM: storage goes to the bricks that hold a domain voxel and lie within ceil((floor(1.001 R / w_min) + 1) / 8) bricks of
+ * one that holds a mask voxel.  12 bytes per brick of the volume, 12812 bytes per brick with storage, what the labelling takes
+ * (8 bytes per voxel and 12 per 64 voxels), 24 bytes per entry of the pair table (the next power of two above twice min(contacts,
+ * n (n - 1) / 2)) and 24 per pair, the inputs and the dense outputs where they are host arrays; everything allocated is freed. */
+int vmask_bridge(int device, const uint8_t* mask, const uint8_t* domain /* may be NULL */, const void* cost, int dtype,
+                 const uint8_t* tips /* may be NULL */, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
+                 double max_cost, int tip_rule, int64_t* counts /* 10, may be NULL */,
+                 int64_t* pairs, double* costs, int64_t cap_pair, int64_t* offsets, int64_t* voxels, int64_t cap_vox,
+                 double* dist /* may be NULL */, int32_t* root /* may be NULL */, uint8_t* pred /* may be NULL */, int32_t* comp /* may be NULL */);
 
 const char* vmask_last_error(void);
 
