@@ -12,17 +12,18 @@
 // not twice.  Contraction is switched off for this whole file by the pragma below (hipcc's default mode honours it); every
 // product and every sum here is its own IEEE operation, on the device and on the host.
 //
-// The volume is cut into 8x8x8 bricks as in vgeo_device.hip.  Storage (a slot: 512 x D, cost, Root, Pred, component word) goes
-// to the bricks that hold a domain voxel and lie within ceil(steps / 8) bricks (Chebyshev) of a brick with a mask voxel, steps =
-// the most edges a path of length <= R can have: R / w_min, w_min the lightest edge the cost volume allows.
+// The volume is cut into 8x8x8 bricks (vbrick.h: the store, its round driver and the hand-off argument).  Storage (a slot: 512 x
+// D, cost, Root, Pred, component word) goes to the bricks that hold a domain voxel and lie within ceil(steps / 8) bricks
+// (Chebyshev) of a brick with a mask voxel, steps = the most edges a path of length <= R can have: R / w_min, w_min the lightest
+// edge the cost volume allows.
 //   k_br_check     every voxel once: counts the domain, the costs that are not finite and positive, the smallest cost; marks
 //                  the bricks that hold a mask voxel and those that hold a domain voxel
 //   k_br_dilate    one axis of the box dilation of the mask's bricks on the brick grid;  k_br_want: dilated and domain
-//   k_br_slots     numbers the wanted bricks;  k_br_init: D, cost, Root of a slot
-//   k_br_list      compacts this round's flags into the list of active bricks (vgeo's k_geo_list)
+//   k_brick_slots  (vbrick.h) numbers the wanted bricks;  k_br_init: D, cost, Root of a slot
+//   k_brick_list   (vbrick.h) compacts this round's flags into the list of active bricks
 //   k_br_flood     one workgroup per active brick: D and cost of the brick + halo in LDS, Jacobi sweeps there, candidates above
-//                  R dropped at once; shell changes flag the bricks that read them - the hand-off argument at the head of
-//                  vgeo_device.hip holds word for word (stored values only decrease, each is the fl-sum along a real path)
+//                  R dropped at once; shell changes flag the bricks that read them - the two conditions of vbrick.h's hand-off
+//                  hold (stored values only decrease, each is the fl-sum along a real path)
 //   k_br_root      the same rounds over Root once D is final: integer minimum over the tight predecessors
 //   k_br_pred      once: Pred, and per voxel the word (component of Root << 1 | Root is a tip) that the contact pass reads
 //   k_br_contact   every voxel looks at its 26 neighbours; the ordered pair (u, v) with comp(Root(u)) < comp(Root(v)) is a
@@ -48,56 +49,24 @@
 
 #include "../../include/vmask.h"
 #include "../../include/vrg.h"
+#include "vbrick.h"
 #include "vmask_cc.h"
-#include "vmask_common.h"
-#include "vmask_host.h"
 
 namespace {
 
 using vmask::CcRank;
 using vmask::cc_rank;
 
-constexpr int TPB = 256;
-constexpr int BRICK = 512;                         // voxels of a brick = threads of a brick's workgroup
-constexpr int HALO = 1000;                         // 10^3: the brick and its one-voxel halo
-constexpr int MAX_SWEEPS = 32;                     // inner sweeps of one brick in one round
-constexpr int GRID_CAP = 65535 * 16;
-constexpr int32_t FREE = -1, OCCUPIED = -2;        // in the brick -> slot grid before the slots are numbered
-constexpr int32_t NO_ROOT = 0x7fffffff;
-constexpr int64_t MAX_ROUNDS = (int64_t)1 << 26;
-constexpr int C_PITCH = 32;                        // every counter keeps 256 bytes to itself
 enum { C_DOMAIN, C_BAD, C_CMIN, C_SLOTS, C_REACHED, C_CONTACTS, C_PAIRS, C_KEPT, C_LIST0, C_LIST1, C_N };
 
-typedef unsigned long long u64;
 constexpr u64 EMPTY = ~0ull;
 
-struct Geo { int32_t n0, n1, n2, B0, B1, B2; };
-
-__device__ __forceinline__ void wave_add(u64* p, u64 v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (v && (threadIdx.x & 63u) == 0u) atomicAdd(p, v);
-}
-
-// brick index and position inside the brick of the voxel with linear index idx
-__device__ __forceinline__ void locate(uint32_t idx, const Geo& g, uint32_t& brick, uint32_t& local) {
-    const uint32_t r = idx / (uint32_t)g.n2, i2 = idx - r * (uint32_t)g.n2, i0 = r / (uint32_t)g.n1, i1 = r - i0 * (uint32_t)g.n1;
-    brick = ((i0 >> 3) * (uint32_t)g.B1 + (i1 >> 3)) * (uint32_t)g.B2 + (i2 >> 3);
-    local = ((i0 & 7u) << 6) | ((i1 & 7u) << 3) | (i2 & 7u);
-}
 // the offset with code k = 0..25: the lexicographic order of (d0, d1, d2) in -1..1 with the centre left out
 __device__ __forceinline__ void offset_of(int k, int& x, int& y, int& z) {
     const int j = k < 13 ? k : k + 1;
     x = j / 9 - 1; y = (j / 3) % 3 - 1; z = j % 3 - 1;
 }
 __device__ __forceinline__ double edge(double cu, double cv, double hw) { const double s = cu + cv; return s * hw; }
-
-// values that another workgroup may store while this one loads them: single relaxed accesses at device scope
-__device__ __forceinline__ double ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ u64 ld(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- the inputs, and the bricks that get storage
 template <class T>
@@ -136,8 +105,8 @@ __global__ void __launch_bounds__(TPB) k_br_check(const uint8_t* __restrict__ ma
 __global__ void __launch_bounds__(TPB) k_br_dilate(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, Geo g, int axis, int32_t r) {
     const uint32_t nbricks = (uint32_t)g.B0 * (uint32_t)g.B1 * (uint32_t)g.B2;
     for (uint32_t b = blockIdx.x * TPB + threadIdx.x; b < nbricks; b += gridDim.x * TPB) {
-        const int32_t b2 = (int32_t)(b % (uint32_t)g.B2), q = (int32_t)(b / (uint32_t)g.B2), b1 = q % g.B1, b0 = q / g.B1;
-        const int32_t c = axis == 0 ? b0 : axis == 1 ? b1 : b2, n = axis == 0 ? g.B0 : axis == 1 ? g.B1 : g.B2;
+        const Brick3 at = brick_coords(b, g);
+        const int32_t c = axis == 0 ? at.b0 : axis == 1 ? at.b1 : at.b2, n = axis == 0 ? g.B0 : axis == 1 ? g.B1 : g.B2;
         const int64_t stride = axis == 0 ? (int64_t)g.B1 * g.B2 : axis == 1 ? g.B2 : 1;
         const int32_t lo = max(0, c - r), hi = min(n - 1, c + r);
         uint8_t any = 0;
@@ -150,30 +119,15 @@ __global__ void __launch_bounds__(TPB) k_br_want(const uint8_t* __restrict__ clo
     for (uint32_t b = blockIdx.x * TPB + threadIdx.x; b < nbricks; b += gridDim.x * TPB) grid[b] = (close_by[b] && dmark[b]) ? OCCUPIED : FREE;
 }
 
-__global__ void __launch_bounds__(TPB) k_br_slots(int32_t* __restrict__ grid, uint32_t nbricks, uint32_t* __restrict__ brick_of, u64* __restrict__ ctr) {
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t b0 = blockIdx.x * TPB; b0 < nbricks; b0 += gridDim.x * TPB) {           // (the same trips in every lane of a wave)
-        const uint32_t b = b0 + threadIdx.x;
-        const bool has = b < nbricks && grid[b] == OCCUPIED;
-        const u64 who = __ballot(has);
-        if (!who) continue;
-        u64 first = 0;
-        if (lane == (uint32_t)(__ffsll((long long)who) - 1)) first = atomicAdd(&ctr[C_SLOTS * C_PITCH], (u64)__popcll(who));
-        first = __shfl(first, __ffsll((long long)who) - 1, 64);
-        const uint32_t slot = (uint32_t)first + (uint32_t)__popcll(who & ((1ull << lane) - 1ull));
-        if (has) { grid[b] = (int32_t)slot; brick_of[slot] = b; }                         // (brick_of holds one entry per brick)
-    }
-}
-
 template <class T>
 __global__ void __launch_bounds__(BRICK) k_br_init(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ domain, const T* __restrict__ cost, Geo g,
                                                    const uint32_t* __restrict__ brick_of, double* __restrict__ D, double* __restrict__ Cst,
                                                    int32_t* __restrict__ Root) {
-    const uint32_t slot = blockIdx.x, t = threadIdx.x, b = brick_of[slot];
-    const uint32_t b2 = b % (uint32_t)g.B2, r = b / (uint32_t)g.B2, b1 = r % (uint32_t)g.B1, b0 = r / (uint32_t)g.B1;
-    const uint32_t i0 = b0 * 8u + (t >> 6), i1 = b1 * 8u + ((t >> 3) & 7u), i2 = b2 * 8u + (t & 7u);
+    const uint32_t slot = blockIdx.x, t = threadIdx.x;
+    const Brick3 here = brick_coords(brick_of[slot], g);
+    const uint32_t i0 = (uint32_t)here.b0 * 8u + (t >> 6), i1 = (uint32_t)here.b1 * 8u + ((t >> 3) & 7u), i2 = (uint32_t)here.b2 * 8u + (t & 7u);
     double d = -1.0, c = 1.0;
-    int32_t root = NO_ROOT;
+    int32_t root = NO_VALUE;
     if (i0 < (uint32_t)g.n0 && i1 < (uint32_t)g.n1 && i2 < (uint32_t)g.n2) {
         const size_t idx = ((size_t)i0 * g.n1 + i1) * g.n2 + i2;
         const bool m = mask[idx] != 0;
@@ -184,65 +138,10 @@ __global__ void __launch_bounds__(BRICK) k_br_init(const uint8_t* __restrict__ m
 }
 
 // ---- one round
-__global__ void __launch_bounds__(TPB) k_br_list(uint32_t* __restrict__ flag, uint32_t nslots, uint32_t* __restrict__ list,
-                                                 u64* __restrict__ cursor, u64* __restrict__ next_cursor) {
-    const uint32_t lane = threadIdx.x & 63u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *next_cursor = 0;
-    for (uint32_t s0 = blockIdx.x * TPB; s0 < nslots; s0 += gridDim.x * TPB) {            // (the same trips in every lane of a wave)
-        const uint32_t s = s0 + threadIdx.x;
-        const bool has = s < nslots && flag[s] != 0u;
-        const u64 who = __ballot(has);
-        if (!who) continue;
-        u64 first = 0;
-        if (lane == (uint32_t)(__ffsll((long long)who) - 1)) first = atomicAdd(cursor, (u64)__popcll(who));
-        first = __shfl(first, __ffsll((long long)who) - 1, 64);
-        if (has) { list[(uint32_t)first + (uint32_t)__popcll(who & ((1ull << lane) - 1ull))] = s; flag[s] = 0u; }
-    }
-}
-
-// What every brick kernel starts with: the slots of the 27 bricks around, then D (+inf outside the domain), the cost and -
-// where asked for - an int32 field of the brick and its halo in LDS.  Ends behind a barrier.
-__device__ __forceinline__ void load_halo(uint32_t b, const Geo& g, const int32_t* __restrict__ grid, const double* D, const double* __restrict__ Cst,
-                                          const int32_t* F, int32_t none, const double* __restrict__ hw,
-                                          double* sD, double* sC, int32_t* sF, double* sH, int32_t* nslot) {
+// the 26 edge weights into LDS (the first barrier of load_halo covers them)
+__device__ __forceinline__ void load_weights(const double* __restrict__ hw, double* sH) {
     const uint32_t t = threadIdx.x;
-    const int32_t b2 = (int32_t)(b % (uint32_t)g.B2), r = (int32_t)(b / (uint32_t)g.B2), b1 = r % g.B1, b0 = r / g.B1;
-    if (t < 27u) {
-        const int32_t c0 = b0 + (int32_t)(t / 9u) - 1, c1 = b1 + (int32_t)((t / 3u) % 3u) - 1, c2 = b2 + (int32_t)(t % 3u) - 1;
-        const bool in = (uint32_t)c0 < (uint32_t)g.B0 && (uint32_t)c1 < (uint32_t)g.B1 && (uint32_t)c2 < (uint32_t)g.B2;
-        nslot[t] = in ? grid[((size_t)c0 * g.B1 + c1) * g.B2 + c2] : -1;
-    }
     if (t >= 32u && t < 58u) sH[t - 32u] = hw[t - 32u];
-    __syncthreads();
-    for (uint32_t q = t; q < (uint32_t)HALO; q += BRICK) {
-        const int32_t la = (int32_t)(q / 100u), rem = (int32_t)(q - (uint32_t)la * 100u), lb = rem / 10, lc = rem - lb * 10;
-        const int32_t ga = la - 1, gb = lb - 1, gc = lc - 1;            // -1 .. 8 relative to the brick
-        const int32_t s = nslot[((ga < 0 ? 0 : ga > 7 ? 2 : 1) * 3 + (gb < 0 ? 0 : gb > 7 ? 2 : 1)) * 3 + (gc < 0 ? 0 : gc > 7 ? 2 : 1)];
-        double v = INFINITY, c = 1.0;
-        int32_t f = none;
-        if (s >= 0) {
-            const size_t at = (size_t)s * BRICK + (size_t)(((ga & 7) << 6) | ((gb & 7) << 3) | (gc & 7));
-            const double d = ld(D + at);
-            if (d >= 0.0) { v = d; c = Cst[at]; if (F) f = ld(F + at); }
-        }
-        sD[q] = v; sC[q] = c;
-        if (F) sF[q] = f;
-    }
-    __syncthreads();
-}
-
-// the bricks that hold the voxel (a, bb, c) of this brick in their halo
-__device__ __forceinline__ void mark_readers(uint32_t a, uint32_t bb, uint32_t c, uint32_t* mark) {
-#pragma unroll
-    for (int x = -1; x <= 1; x++)
-#pragma unroll
-        for (int y = -1; y <= 1; y++)
-#pragma unroll
-            for (int z = -1; z <= 1; z++) {
-                if (!x && !y && !z) continue;
-                if ((x < 0 && a != 0u) || (x > 0 && a != 7u) || (y < 0 && bb != 0u) || (y > 0 && bb != 7u) || (z < 0 && c != 0u) || (z > 0 && c != 7u)) continue;
-                mark[(x + 1) * 9 + (y + 1) * 3 + (z + 1)] = 1u;
-            }
 }
 
 __global__ void __launch_bounds__(BRICK) k_br_flood(const uint32_t* __restrict__ list, const uint32_t* __restrict__ brick_of, const int32_t* __restrict__ grid,
@@ -253,9 +152,9 @@ __global__ void __launch_bounds__(BRICK) k_br_flood(const uint32_t* __restrict__
     __shared__ uint32_t mark[27];
     const uint32_t t = threadIdx.x, slot = list[blockIdx.x];
     if (t < 27u) mark[t] = 0u;
-    load_halo(brick_of[slot], g, grid, D, Cst, nullptr, 0, hw, sD, sC, nullptr, sH, nslot);
-    const uint32_t a = t >> 6, bb = (t >> 3) & 7u, c = t & 7u;
-    const int32_t me = (int32_t)((a + 1u) * 100u + (bb + 1u) * 10u + (c + 1u));
+    load_weights(hw, sH);
+    load_halo<true, false>(brick_of[slot], g, grid, D, Cst, nullptr, 0, sD, sC, nullptr, nslot);
+    const int32_t me = halo_at(t);
     const size_t mine = (size_t)slot * BRICK + t;
     const double d0 = D[mine], cme = sC[me];                            // (only this workgroup stores to its brick)
     const bool in = d0 > 0.0;                                           // in the domain and no source
@@ -285,10 +184,8 @@ __global__ void __launch_bounds__(BRICK) k_br_flood(const uint32_t* __restrict__
         if (!any) break;
     }
     const bool changed = in && cur < d0;
-    if (changed) { st(D + mine, cur); mark_readers(a, bb, c, mark); }
-    __syncthreads();
-    if (t < 27u && t != 13u && mark[t] && nslot[t] >= 0) flag_next[nslot[t]] = 1u;
-    if (t == 13u && any) flag_next[slot] = 1u;                          // the sweeps ran out: this brick goes on in the next round
+    if (changed) st(D + mine, cur);
+    mark_readers(changed, any, slot, nslot, mark, flag_next);
 }
 
 // bit k: the neighbour with code k is a tight predecessor of the voxel at `me`
@@ -319,39 +216,17 @@ __global__ void __launch_bounds__(BRICK) k_br_root(const uint32_t* __restrict__ 
     __shared__ uint32_t mark[27];
     const uint32_t t = threadIdx.x, slot = list[blockIdx.x];
     if (t < 27u) mark[t] = 0u;
-    load_halo(brick_of[slot], g, grid, D, Cst, Root, NO_ROOT, hw, sD, sC, sL, sH, nslot);
-    const uint32_t a = t >> 6, bb = (t >> 3) & 7u, c = t & 7u;
-    const int32_t me = (int32_t)((a + 1u) * 100u + (bb + 1u) * 10u + (c + 1u));
+    load_weights(hw, sH);
+    load_halo<true, true>(brick_of[slot], g, grid, D, Cst, Root, NO_VALUE, sD, sC, sL, nslot);
+    const int32_t me = halo_at(t);
     const size_t mine = (size_t)slot * BRICK + t;
     const double d0 = D[mine];
     const uint32_t tight = (d0 > 0.0 && d0 < INFINITY) ? tight_bits(sD, sC, sH, me, d0) : 0u;
-    const int32_t l0 = Root[mine];
-    int32_t cur = l0;
-    bool any = false;
-    for (int sweep = 0; sweep < MAX_SWEEPS; sweep++) {
-        int32_t best = cur;
-        int k = 0;
-#pragma unroll
-        for (int x = -1; x <= 1; x++)
-#pragma unroll
-            for (int y = -1; y <= 1; y++)
-#pragma unroll
-                for (int z = -1; z <= 1; z++) {
-                    if (!x && !y && !z) continue;
-                    if (tight & (1u << k)) best = min(best, sL[me + x * 100 + y * 10 + z]);
-                    k++;
-                }
-        const bool better = best < cur;
-        any = __syncthreads_or(better) != 0;
-        if (better) { cur = best; sL[me] = best; }
-        __syncthreads();
-        if (!any) break;
-    }
+    bool any;
+    const int32_t l0 = Root[mine], cur = min_over_tight(tight, l0, sL, me, any);
     const bool changed = cur < l0;
-    if (changed) { st(Root + mine, cur); mark_readers(a, bb, c, mark); }
-    __syncthreads();
-    if (t < 27u && t != 13u && mark[t] && nslot[t] >= 0) flag_next[nslot[t]] = 1u;
-    if (t == 13u && any) flag_next[slot] = 1u;
+    if (changed) st(Root + mine, cur);
+    mark_readers(changed, any, slot, nslot, mark, flag_next);
 }
 
 // one workgroup per slot, once D and Root are final
@@ -363,8 +238,9 @@ __global__ void __launch_bounds__(BRICK) k_br_pred(const uint32_t* __restrict__ 
     __shared__ int32_t sL[HALO];
     __shared__ int32_t nslot[27];
     const uint32_t t = threadIdx.x, slot = blockIdx.x;
-    load_halo(brick_of[slot], g, grid, D, Cst, Root, NO_ROOT, hw, sD, sC, sL, sH, nslot);
-    const int32_t me = (int32_t)(((t >> 6) + 1u) * 100u + (((t >> 3) & 7u) + 1u) * 10u + ((t & 7u) + 1u));
+    load_weights(hw, sH);
+    load_halo<true, true>(brick_of[slot], g, grid, D, Cst, Root, NO_VALUE, sD, sC, sL, nslot);
+    const int32_t me = halo_at(t);
     const size_t mine = (size_t)slot * BRICK + t;
     const double d0 = D[mine];
     const int32_t root = sL[me];
@@ -386,7 +262,7 @@ __global__ void __launch_bounds__(BRICK) k_br_pred(const uint32_t* __restrict__ 
     }
     Pred[mine] = (uint8_t)code;
     int32_t cid = 0;
-    if (d0 >= 0.0 && root != NO_ROOT) cid = (int32_t)(((cc_rank(rk, (uint32_t)ccroot[root]) + 1u) << 1) | ((!tips || tips[root]) ? 1u : 0u));
+    if (d0 >= 0.0 && root != NO_VALUE) cid = (int32_t)(((cc_rank(rk, (uint32_t)ccroot[root]) + 1u) << 1) | ((!tips || tips[root]) ? 1u : 0u));
     Cid[mine] = cid;
     wave_add(&ctr[C_REACHED * C_PITCH], reached ? 1ull : 0ull);
 }
@@ -403,13 +279,13 @@ __global__ void __launch_bounds__(BRICK) k_br_contact(const uint32_t* __restrict
     __shared__ int32_t sI[HALO];
     __shared__ int32_t nslot[27];
     const uint32_t t = threadIdx.x, slot = blockIdx.x, b = brick_of[slot];
-    load_halo(b, g, grid, D, Cst, Cid, 0, hw, sD, sC, sI, sH, nslot);
-    const uint32_t la = t >> 6, lb = (t >> 3) & 7u, lc = t & 7u;
-    const int32_t me = (int32_t)((la + 1u) * 100u + (lb + 1u) * 10u + (lc + 1u));
+    load_weights(hw, sH);
+    load_halo<true, true>(b, g, grid, D, Cst, Cid, 0, sD, sC, sI, nslot);
+    const int32_t me = halo_at(t);
     const int32_t ime = sI[me];
     const double dme = sD[me], cme = sC[me];
-    const uint32_t b2 = b % (uint32_t)g.B2, r = b / (uint32_t)g.B2, b1 = r % (uint32_t)g.B1, b0 = r / (uint32_t)g.B1;
-    const u64 idx = ((u64)(b0 * 8u + la) * (u64)g.n1 + (b1 * 8u + lb)) * (u64)g.n2 + (b2 * 8u + lc);
+    const Brick3 here = brick_coords(b, g);
+    const u64 idx = ((u64)((uint32_t)here.b0 * 8u + (t >> 6)) * (u64)g.n1 + ((uint32_t)here.b1 * 8u + ((t >> 3) & 7u))) * (u64)g.n2 + ((uint32_t)here.b2 * 8u + (t & 7u));
     u64 found = 0;
     if (ime != 0) {                                                     // (then D is finite: Root exists)
         const uint32_t ca = (uint32_t)ime >> 1, tipa = (uint32_t)ime & 1u;
@@ -535,8 +411,6 @@ __global__ void __launch_bounds__(TPB) k_br_scatter(Geo g, u64 V, const int32_t*
     }
 }
 
-int grid_for(u64 items, u64 cap) { return (int)std::max<u64>(1, std::min<u64>(cap, items)); }
-
 struct CcHold {                                                         // (the labelling's arrays are freed on every return)
     vmask::CcOut c;
     ~CcHold() { vmask::cc_release(c); }
@@ -547,28 +421,6 @@ struct Bricks {                                                         // (name
     int32_t* Root = nullptr; uint8_t* Pred = nullptr; int32_t* Cid = nullptr; uint32_t* flag = nullptr; uint32_t* list = nullptr;
     const double* hw = nullptr;
 };
-
-// the fixed point of one kind: rounds until no brick is flagged; flags of the first round are in flag[0 .. nslots)
-template <int ROOTS>
-int iterate(const Bricks& b, uint32_t nslots, const Geo& g, double R, int64_t& rounds) {
-    const int glist = grid_for(((u64)nslots + TPB - 1) / TPB, 1024);
-    int cur = 0;
-    for (rounds = 0;; rounds++) {
-        if (rounds == MAX_ROUNDS) { vmask::set_error("the relaxation did not finish"); return VRG_E_INTERNAL; }
-        u64* cursor = b.ctr + (size_t)(C_LIST0 + (int)(rounds & 1)) * C_PITCH;
-        u64* other = b.ctr + (size_t)(C_LIST0 + (int)((rounds + 1) & 1)) * C_PITCH;
-        k_br_list<<<glist, TPB>>>(b.flag + (size_t)cur * nslots, nslots, b.list, cursor, other);
-        u64 active = 0;
-        VMASK_TRY(hipMemcpy(&active, cursor, sizeof(u64), hipMemcpyDeviceToHost));
-        if (!active) break;
-        uint32_t* next = b.flag + (size_t)(cur ^ 1) * nslots;
-        if (ROOTS) k_br_root<<<(uint32_t)active, BRICK>>>(b.list, b.brick_of, b.grid, g, b.hw, b.D, b.Cst, b.Root, next);
-        else k_br_flood<<<(uint32_t)active, BRICK>>>(b.list, b.brick_of, b.grid, g, b.hw, R, b.D, b.Cst, next);
-        cur ^= 1;
-    }
-    VMASK_TRY(hipGetLastError());
-    return VRG_OK;
-}
 
 struct Args {
     const uint8_t* mask; const uint8_t* domain; const void* cost; int dtype; const uint8_t* tips;
@@ -628,11 +480,8 @@ int bridge(const Args& a, Geo g, const double* hw_host) {
     k_br_dilate<<<gb, TPB>>>(w1, w0, g, 2, reach);
     k_br_want<<<gb, TPB>>>(w0, dmark, nbricks, b.grid);
     VMASK_GRAB(b.brick_of, nbricks, "brick list");
-    k_br_slots<<<gb, TPB>>>(b.grid, nbricks, b.brick_of, b.ctr);
-    u64 found = 0;
-    VMASK_TRY(hipMemcpy(&found, b.ctr + (size_t)C_SLOTS * C_PITCH, sizeof(u64), hipMemcpyDeviceToHost));
-    if (found > nbricks) { vmask::set_error("more slots than bricks"); return VRG_E_INTERNAL; }
-    const uint32_t nslots = (uint32_t)found;
+    uint32_t nslots = 0;                                                // (brick_of holds one entry per brick)
+    if ((rc = number_bricks(b.grid, nbricks, nbricks, b.brick_of, b.ctr + c_at(C_SLOTS), "more slots than bricks", nslots))) return rc;
     mem.drop(marks);
     int64_t rounds[2] = {0, 0};
     u64 reached = 0, contacts = 0, npairs = 0, nkept = 0;
@@ -652,7 +501,10 @@ int bridge(const Args& a, Geo g, const double* hw_host) {
         for (int pass = 0; pass < 2; pass++) {                          // every brick looks once, then as flagged
             VMASK_TRY(hipMemsetAsync(b.flag, 0, (size_t)2 * nslots * sizeof(uint32_t), 0));
             VMASK_TRY(hipMemsetAsync(b.flag, 1, (size_t)nslots * sizeof(uint32_t), 0));          // (0x01010101: not 0)
-            rc = pass ? iterate<1>(b, nslots, g, R, rounds[1]) : iterate<0>(b, nslots, g, R, rounds[0]);
+            rc = iterate(b.flag, b.list, b.ctr + c_at(C_LIST0), nslots, rounds[pass], [&](const uint32_t* list, uint32_t active, uint32_t* flag_next) {
+                if (pass) k_br_root<<<active, BRICK>>>(list, b.brick_of, b.grid, g, b.hw, b.D, b.Cst, b.Root, flag_next);
+                else k_br_flood<<<active, BRICK>>>(list, b.brick_of, b.grid, g, b.hw, R, b.D, b.Cst, flag_next);
+            });
             if (rc) return rc;
         }
         k_br_pred<<<nslots, BRICK>>>(b.brick_of, b.grid, g, b.hw, b.D, b.Cst, b.Root, hold.c.root, hold.c.rank(), dtips, b.Pred, b.Cid, b.ctr);
@@ -763,9 +615,7 @@ extern "C" int vmask_bridge(int device, const uint8_t* mask, const uint8_t* doma
         volatile double s = xx + yy;
         hw[k] = 0.5 * std::sqrt(s + zz);
     }
-    Geo g;
-    g.n0 = (int32_t)n0; g.n1 = (int32_t)n1; g.n2 = (int32_t)n2;
-    g.B0 = (g.n0 + 7) / 8; g.B1 = (g.n1 + 7) / 8; g.B2 = (g.n2 + 7) / 8;
     const Args a{mask, domain, cost, dtype, tips, max_cost, tip_rule, counts, pairs, costs, cap_pair, offsets, voxels, cap_vox, dist, root, pred, comp};
+    const Geo g = make_geo(n0, n1, n2);
     return dtype == VRG_F32 ? bridge<float>(a, g, hw) : bridge<double>(a, g, hw);
 }

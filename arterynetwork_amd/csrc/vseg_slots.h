@@ -1,7 +1,8 @@
 // vseg_slots.h - what the passes over the compacted object voxels ("slots") share: vseg_device.hip (segment tracing) and
 // vbr_device.hip (branch graph).  The volume is read as a flat byte string in aligned 16-byte words, its object voxels are
-// counted, listed (one atomic per wave) and entered idx -> slot into an open-addressing hash table; the wave helpers and the
-// 27-bit neighbourhood numbering of those translation units (their host-side helpers: vmask_host.h).  Everything has internal linkage.
+// counted, listed (one atomic per wave) and entered idx -> slot into an open-addressing hash table; the 27-bit neighbourhood
+// numbering of those translation units (wave helpers and the word read: vmask_wave.h, host-side helpers: vmask_host.h).
+// Everything has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include "../../include/vrg.h"
 #include "vmask_common.h"
 #include "vmask_host.h"
+#include "vmask_wave.h"
 
 namespace {
 
@@ -19,41 +21,9 @@ constexpr int TPB = 256;
 constexpr int GRID_VOLUME = 2048;                  // blocks, at most, of the two kernels that read the volume (16 bytes per thread and turn)
 constexpr int GRID_LIST = 256;                     // blocks, at most, of the kernels over slots, darts and segment heads
 
-typedef unsigned long long u64;
-
-// counters on the device sit 256 bytes apart: each is added to by every wave that has something to add
-constexpr int C_PITCH = 32;
-__host__ __device__ inline int c_at(int k) { return k * C_PITCH; }
-
 struct Dim { int32_t n0, n1, n2; };
 
 constexpr uint32_t NONE = 0xffffffffu;
-
-// ---- wave helpers (every lane of the wave must call them)
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ void wave_add(u64* ctr, u64 x) {
-    x = wave_sum(x);
-    if (x && lane_id() == 0u) atomicAdd(ctr, x);
-}
-// exclusive prefix sum of x over the wave's lanes; total = the wave's sum
-__device__ __forceinline__ uint32_t wave_scan(uint32_t x, uint32_t& total) {
-    uint32_t v = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(v, o, 64); if (lane_id() >= (uint32_t)o) v += y; }
-    total = __shfl(v, 63, 64);
-    return v - x;
-}
-// room for `total` entries behind the cursor, the wave's first entry returned to every lane
-__device__ __forceinline__ u64 wave_reserve(u64* cursor, uint32_t total) {
-    u64 at = 0;
-    if (lane_id() == 0u) at = atomicAdd(cursor, (u64)total);
-    return __shfl(at, 0, 64);
-}
 
 // ---- idx -> slot: open addressing, linear probing, at most half full; entry = idx << 32 | slot
 struct Hash { u64* tab; uint32_t mask, shift; };
@@ -80,23 +50,7 @@ inline int hash_bits(uint32_t n) {
     return bits;
 }
 
-// ---- the volume as a flat byte string read in aligned 16-byte words
-// bit k of the result: byte k of the word is != 0
-__device__ __forceinline__ uint32_t nz4(uint32_t w) {
-    const uint32_t h = (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
-    return ((h >> 7) & 1u) | ((h >> 14) & 2u) | ((h >> 21) & 4u) | ((h >> 28) & 8u);
-}
-// word b of the aligned string covers voxels 16 b - lead .. + 15: the 16-bit mask of its object voxels, those outside [0, V) dropped
-__device__ __forceinline__ uint32_t word_mask(const uint4* __restrict__ base, u64 b, uint32_t lead, u64 V) {
-    const uint4 w = base[b];
-    if (!(w.x | w.y | w.z | w.w)) return 0u;
-    uint32_t m = nz4(w.x) | (nz4(w.y) << 4) | (nz4(w.z) << 8) | (nz4(w.w) << 12);
-    const int64_t f0 = (int64_t)(16 * b) - (int64_t)lead, left = (int64_t)V - f0;    // (left >= 1)
-    if (f0 < 0) m &= ~((1u << (uint32_t)(-f0)) - 1u);
-    if (left < 16) m &= (1u << (uint32_t)left) - 1u;
-    return m;
-}
-
+// ---- the object voxels, counted and listed
 __global__ void __launch_bounds__(TPB) k_seg_count(const uint4* __restrict__ base, u64 nwords, uint32_t lead, u64 V, u64* __restrict__ c_obj) {
     u64 n = 0;
     for (u64 b = (u64)blockIdx.x * TPB + threadIdx.x; b < nwords; b += (u64)gridDim.x * TPB) n += (u64)__popc(word_mask(base, b, lead, V));

@@ -238,7 +238,7 @@ def test_brick_seams(a, c, through):
 def test_more_sweeps_than_one_round():
     """A serpentine corridor of domain inside one brick, a source at each end: either flood runs for more steps than a
     workgroup sweeps in one round, so the brick has to flag itself."""
-    src = open(os.path.join(ROOT, 'arterynetwork_amd', 'csrc', 'vbridge_device.hip')).read()
+    src = open(os.path.join(ROOT, 'arterynetwork_amd', 'csrc', 'vbrick.h')).read()
     cap = int(re.search(r'constexpr int MAX_SWEEPS = (\d+);', src).group(1))
     dom, order = _serpentine(8)
     assert len(order) // 2 > cap + 8

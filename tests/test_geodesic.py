@@ -284,7 +284,7 @@ def test_geodesic_kernels_use_no_scratch_and_few_registers(tmp_path):
     for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.wavefront_size', out.read_text(), re.S):      # the metadata records only
         recs[m.group(1)] = (int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', m.group(2)).group(1)),
                             int(re.search(r'\.vgpr_count:\s+(\d+)', m.group(2)).group(1)))
-    for frag in ('k_geo_mark', 'k_geo_slots', 'k_geo_init', 'k_geo_check', 'k_geo_seed', 'k_geo_list', 'k_geo_relaxILi0E', 'k_geo_relaxILi1E',
+    for frag in ('k_geo_mark', 'k_brick_slots', 'k_geo_init', 'k_geo_check', 'k_geo_seed', 'k_brick_list', 'k_geo_relaxILi0E', 'k_geo_relaxILi1E',
                  'k_geo_scatter'):
         assert sum(frag in k for k in recs) == 1, 'kernel not found: ' + frag
     for name, (scratch, vgprs) in recs.items():

@@ -100,7 +100,7 @@ def main():
                     'synchronise), {} warm call, then the median (min - max) of {}. Workload 1 is `geodesicTerritories` with every centre-line voxel of a '
                     'segment as a seed (labels, sizes and distance); workload 2 is `geodesicDistance` from one seed at the end of the longest segment '
                     '(distance only). `vmask_territories` on the same mask and one streaming read of the mask (`int64` view, `sum`) run in the same '
-                    'process (HIP events) as the yardstick. Rounds: distance / label rounds, each one `k_geo_list` + one `k_geo_relax` launch and one 8-byte '
+                    'process (HIP events) as the yardstick. Rounds: distance / label rounds, each one `k_brick_list` (csrc/vbrick.h) + one `k_geo_relax` launch and one 8-byte '
                     'read-back. Work space: 4 bytes per brick of the volume plus 6160 (4112 without labels) per occupied brick; the dense outputs are the '
                     'caller\'s. No time was set as a target.\n\n'.format(''.join(' --shape ' + s for s in a.shape), WARM, REPS))
             f.write('| volume | mask | mask voxels | segments | occupied bricks | all seeds ms | rounds D / labels | ms per round | work MB | one seed ms | rounds | ms per round | '
