@@ -145,6 +145,39 @@ def model(mask, cost, domain=None, tips=None, spacing=None, max_cost=16.0, tip_r
     return r
 
 
+def brick_any(a):
+    """Which 8x8x8 bricks of the boolean volume a hold a set voxel: a boolean array over the brick grid."""
+    B = tuple((n + 7) // 8 for n in a.shape)
+    P = np.zeros(tuple(8 * b for b in B), bool)
+    P[:a.shape[0], :a.shape[1], :a.shape[2]] = a
+    return P.reshape(B[0], 8, B[1], 8, B[2], 8).any(axis=(1, 3, 5))
+
+
+def expected_bricks(mask, cost, domain=None, spacing=None, max_cost=16.0):
+    """The storage rule that include/vmask.h states under VRG_E_MEM, from its text: storage goes to the bricks that hold a voxel
+    of the effective domain and lie within `reach` bricks (Chebyshev) of one that holds a mask voxel, reach =
+    min(max(B0, B1, B2), ceil(steps / 8)), steps = floor(1.001 R / w_min) + 1, w_min = fl(fl(2 c_min) min hw), c_min the
+    smallest cost in the effective domain.  Returns (stored, facts): the boolean brick grid, and a dict with `ratio` =
+    1.001 R / w_min as computed here (the caller keeps it away from the integers: floor and ceil are then the host's whatever
+    the order of its roundings), `steps`, `reach` and `domain_bricks`."""
+    m, dom, c, hw, W = setup(mask, domain, cost, spacing)
+    mb, db = brick_any(m), brick_any(dom)
+    B = mb.shape
+    ratio, steps, reach = 0.0, 0, 0
+    if dom.any():
+        c_min = c[dom].min()
+        w_min = (c_min + c_min) * hw.min()
+        ratio = float(1.001 * (0.5 * max_cost) / w_min)
+        steps = int(np.floor(ratio)) + 1
+        reach = min(max(B), -(-steps // 8))
+    b0, b1, b2 = np.nonzero(mb)
+    g0, g1, g2 = np.indices(B)
+    close = np.zeros(B, bool)
+    for p, q, r in zip(b0, b1, b2):                # one box per mask brick: nothing here is separable, strided or clamped
+        close |= np.maximum(np.maximum(np.abs(g0 - p), np.abs(g1 - q)), np.abs(g2 - r)) <= reach
+    return close & db, dict(ratio=ratio, steps=steps, reach=reach, domain_bricks=int(db.sum()))
+
+
 def dijkstra(mask, cost, domain=None, spacing=None, max_cost=16.0):
     """(dist, root, pred) as `model` gives them, by a heap over (D, voxel) and Python loops; Root and Pred in the order of
     increasing D, which is well founded because every weight is positive.  Nothing is shared with `model` but OFFSETS: the

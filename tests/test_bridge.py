@@ -1,7 +1,8 @@
 """Minimal-cost bridges between vessel fragments ("f19 bridges"): the numpy model tests/bridge_model.py is
 checked on the CPU against a heap Dijkstra, then vmask_bridge / reconnect.bridgeCandidates must equal it exactly - the bits of
 dist, root, pred, pairs, costs, offsets, voxels and counts[0..6] - on shapes off the brick grid, under ties, at the bound,
-across brick seams, through long corridors and with thousands of pairs; then the recovery phantom and the file-level driver."""
+across brick seams, through long corridors and with thousands of pairs, with storage on a fraction of a non-cubic brick grid, a
+pair table whose probes wrap and a result beyond the first call's capacity; then the recovery phantom and the file-level driver."""
 import functools
 import os
 import re
@@ -183,6 +184,151 @@ def test_python_argument_checks():
         R.tipRegions(m, reach=-1.0)
 
 
+# ------------------------------------------------------------------ CPU: what the sparse, wrapped and resized cases rest on
+# Storage on the 5 x 3 x 9 brick grid of a 40 x 24 x 72 volume.  name: mask points, max_cost, spacing, float32 cost, domain with
+# two empty slabs, then what the header's rule gives: reach, bricks with storage, bricks that hold a domain voxel
+SPARSE_SHAPE = (40, 24, 72)
+SPARSE = {
+    'interior': ([(17, 9, 30), (17, 9, 35)], 6.0, None, False, False, (1, 36, 135)),
+    'interior_float32': ([(17, 9, 30), (17, 9, 35)], 6.0, None, True, False, (1, 36, 135)),
+    'reach_2': ([(17, 9, 30), (17, 9, 38)], 9.5, None, False, False, (2, 90, 135)),
+    'volume_corners': ([(0, 0, 0), (3, 2, 4), (39, 23, 71), (36, 21, 68)], 6.0, None, False, False, (1, 16, 135)),
+    'brick_corner_seam': ([(23, 15, 39), (24, 16, 43), (23, 15, 47)], 6.0, None, False, False, (1, 42, 135)),
+    'empty_domain_bricks': ([(17, 9, 30), (17, 9, 35), (20, 4, 33)], 6.0, None, False, True, (1, 22, 104)),
+    'anisotropic': ([(17, 9, 30), (17, 9, 42), (18, 11, 31)], 2.5, (2.0, 1.0, 0.25), False, False, (2, 105, 135)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _sparse(name):
+    """The inputs of one case, the model's result and the header's storage rule (BM.expected_bricks); tip_rule 0."""
+    pts, max_cost, spacing, f32, cut, _ = SPARSE[name]
+    cost = np.random.default_rng(21).uniform(0.5, 1.0, SPARSE_SHAPE)
+    if f32:
+        cost = cost.astype(np.float32)
+    dom = None
+    if cut:
+        dom = np.ones(SPARSE_SHAPE, np.uint8)
+        dom[8:16] = 0                                                  # brick plane 1 of axis 0
+        dom[:, 16:24, 24:32] = 0                                       # and the bricks (., 2, 3)
+    mask = _points(SPARSE_SHAPE, pts)
+    ref = BM.model(mask, cost, dom, None, spacing, max_cost, 0)
+    stored, facts = BM.expected_bricks(mask, cost, dom, spacing, max_cost)
+    return mask, cost, dom, spacing, max_cost, ref, stored, facts
+
+
+@pytest.mark.parametrize('name', list(SPARSE))
+def test_sparse_cases_are_sparse_and_sufficient(name):
+    """Before any device runs: the rule leaves domain bricks without storage (else the case tests nothing), its floor and ceil
+    are a margin away from where rounding could move them, and no brick that the model uses - one with a mask voxel or a reached
+    one - is left out."""
+    mask, cost, dom, spacing, max_cost, ref, stored, facts = _sparse(name)
+    reach, nstored, ndomain = SPARSE[name][5]
+    assert abs(facts['ratio'] - round(facts['ratio'])) >= 0.005 and facts['steps'] not in (8, 9, 16, 17)
+    assert stored.shape == (5, 3, 9) and facts['reach'] == reach
+    assert int(stored.sum()) < facts['domain_bricks']
+    assert (int(stored.sum()), facts['domain_bricks']) == (nstored, ndomain)
+    used = BM.brick_any((ref.dist >= 0.0) & np.isfinite(ref.dist))     # D = 0 in the mask, finite where reached
+    assert used.any() and not (used & ~stored).any()
+    if name == 'interior':
+        assert not stored[0, 0, 0] and ref.dist[2, 2, 2] == np.inf and ref.root[2, 2, 2] == -1 and ref.pred[2, 2, 2] == 255
+    if name == 'reach_2':                                              # axis 0: all 5, axis 1: its 3 (the clamp bites), axis 2: 6 of 9
+        assert [int(stored.any(axis=ax).sum()) for ax in ((1, 2), (0, 2), (0, 1))] == [5, 3, 6]
+    if name == 'volume_corners':                                       # clamped at both ends of every axis
+        assert stored[0, 0, 0] and stored[4, 2, 8] and stored[1, 1, 1] and stored[3, 1, 7] and not stored[2].any()
+    if name == 'brick_corner_seam':
+        assert ref.counts[5] == 2 and ref.counts[3] == 605 and int(used.sum()) == 12
+    if name == 'empty_domain_bricks':                                  # bricks within reach that hold no domain voxel get no slot
+        whole, wfacts = BM.expected_bricks(mask, cost, None, spacing, max_cost)
+        assert wfacts['reach'] == reach and int((whole & ~stored).sum()) == 36 - 22 and ref.counts[5] == 3
+    if name == 'anisotropic':                                          # the lightest edge runs along axis 2
+        assert int(np.argmin(BM.half_weights(spacing))) in (12, 13) and ref.counts[4] == 3 and ref.counts[5] == 2
+
+
+def _pair_table_source():
+    """The pair table's hash and its smallest size, read from the kernel source: hash(key, bits), the minimum of bits."""
+    src = open(os.path.join(ROOT, 'arterynetwork_amd', 'csrc', 'vbridge_device.hip')).read()
+    mo = re.search(r'hash_of\(u64 key, uint32_t bits\) \{ return \(uint32_t\)\(\(key \* (0x[0-9A-Fa-f]+)ull\) >> \((\d+)u - bits\)\); \}', src)
+    mult, width = int(mo.group(1), 16), int(mo.group(2))
+    assert width == 64
+    least = int(re.search(r'uint32_t tbits = (\d+);\s*while \(\(\(u64\)1 << tbits\) < 2 \* most\) tbits\+\+;', src).group(1))
+    return (lambda key, bits: ((key * mult) & ((1 << 64) - 1)) >> (width - bits)), least
+
+
+@functools.lru_cache(maxsize=None)
+def _line(npairs):
+    """1 x 1 x N, cost 1, max_cost 4 (R = 2): 1100 single-voxel components; component i (1-based) is followed by 3 free voxels
+    if i is among the first `npairs` i with hash(i << 32 | i + 1, 6) >= 62, else by 6.  Three free voxels have D = 1, 2, 1 and one
+    contact; of six the third would need D = 3 > R: no contact.  Returns the mask, those i and the model's result."""
+    hash_of, least = _pair_table_source()
+    assert least == 6
+    late = [i for i in range(1, 1100) if hash_of(i << 32 | i + 1, 6) >= 62]
+    assert len(late) == 34 and late[:3] == [38, 64, 90] and late[-1] == 1079
+    chosen = late[:npairs]
+    at, z = [], 0
+    for i in range(1, 1101):
+        at.append(z)
+        z += 4 if i in chosen else 7
+    mask = np.zeros((1, 1, z), np.uint8)
+    mask[0, 0, at] = 1
+    return mask, chosen, BM.model(mask, np.ones(mask.shape), None, None, None, 4.0, 0)
+
+
+def _probed(homes, entries):
+    """Linear probing of `homes` in this order into an empty table: the occupied entries, the longest probe."""
+    taken, longest = set(), 0
+    for h in homes:
+        steps = 0
+        while (h + steps) % entries in taken:
+            steps += 1
+        taken.add((h + steps) % entries)
+        longest = max(longest, steps)
+    return taken, longest
+
+
+def test_pair_table_certificate():
+    """What test_pair_table_wraps rests on: 32 pairs make the smallest table (64 entries) exactly half full, every pair's home
+    is entry 62 or 63, so whatever the order of insertion 30 entries wrap past the table's end and the last pair probes 30 or 31
+    times - and phase 2 has to walk the same way to find it.  33 pairs take the sizing loop's first step, to 128 entries."""
+    hash_of, least = _pair_table_source()
+    mask, chosen, ref = _line(32)
+    assert mask.shape == (1, 1, 7604) and ref.counts.tolist() == [1100, 7604, 4366, 32, 32, 32, 160]
+    assert ref.pairs[:, :2].tolist() == [[i, i + 1] for i in chosen]
+    most = min(int(ref.counts[3]), 1100 * 1099 // 2)
+    assert most == 32 and 2 * 32 == 64 == 1 << least                   # the loop `while (1 << tbits) < 2 * most` stays at 6
+    homes = [hash_of(int(a) << 32 | int(b), 6) for a, b in ref.pairs[:, :2]]
+    assert sorted(set(homes)) == [62, 63] and homes.count(62) == 15 and homes.count(63) == 17
+    rng = np.random.default_rng(0)
+    for order in (homes, homes[::-1], sorted(homes), sorted(homes)[::-1], rng.permutation(homes).tolist()):
+        taken, longest = _probed(order, 64)
+        assert taken == {62, 63} | set(range(30)) and longest in (30, 31)
+        assert sum(e < 62 for e in taken) == 30                       # 30 entries wrap past the table's end
+    mask, chosen, ref = _line(33)
+    assert mask.shape == (1, 1, 7601) and ref.counts[3:6].tolist() == [33, 33, 33]
+    assert (1 << 6) < 2 * 33 <= (1 << 7)                              # 128 entries
+    homes = [hash_of(int(a) << 32 | int(b), 7) for a, b in ref.pairs[:, :2]]
+    assert all(h >> 1 in (62, 63) for h in homes) and _probed(homes, 128)[0] <= set(range(124, 128)) | set(range(29))
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_36():
+    """Single-voxel components on a 3-spaced lattice in 36^3: more bridges than the tables of the first call hold."""
+    shape = (36, 36, 36)
+    mask = np.zeros(shape, np.uint8)
+    mask[1::3, 1::3, 1::3] = 1
+    cost = np.random.default_rng(5).uniform(0.5, 1.0, shape)
+    return mask, cost, BM.model(mask, cost, None, None, None, 4.5, 0)
+
+
+def test_second_call_case_crosses_the_pair_capacity_only():
+    src = open(os.path.join(ROOT, 'arterynetwork_amd', 'reconnect.py')).read()
+    mo = re.search(r'cap_pair, cap_vox = (\d+), 1 << (\d+) ', src)
+    assert (int(mo.group(1)), int(mo.group(2))) == (4096, 18)
+    mask, cost, ref = _lattice_36()
+    assert ref.counts[[0, 4, 5, 6]].tolist() == [1728, 18781, 18433, 73732]
+    assert ref.counts[5] > 4096 and ref.counts[6] < 1 << 18
+
+
 # ------------------------------------------------------------------ GPU
 SHAPES = [(8, 8, 8), (9, 17, 23), (1, 1, 40), (3, 5, 70), (20, 24, 40)]
 
@@ -245,6 +391,7 @@ def test_more_sweeps_than_one_round():
     mask = _points((8, 8, 8), [order[0], order[-1]])
     b, info, ref = _check(mask, np.ones((8, 8, 8)), dom, None, None, 2.0 * len(order), 0)
     assert info['bricks'] == 1 and info['flood_rounds'] >= 2 and len(b) == 1
+    assert info['root_rounds'] >= 2                                    # Root moves one voxel a sweep along either chain: that pass runs out too
     half = b.voxels.tolist().index(int(b.ends[0, 0])) + 1              # the entries of u's chain; the rest is v's
     assert half - 1 > cap and len(b.voxels) - half - 1 > cap
 
@@ -280,6 +427,54 @@ def test_many_pairs():
     cost = np.random.default_rng(5).uniform(0.5, 1.0, shape)
     b, info, ref = _check(mask, cost, None, None, None, 4.5, 0)
     assert info['components'] == 1728 and info['pairs'] > 4000 and len(b) > 2000
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', list(SPARSE))
+def test_sparse_storage(name):
+    """Storage on a 5 x 3 x 9 brick grid where most domain bricks get none: the three axes of the dilation with their strides
+    and clamps, bricks within reach without a domain voxel, halo loads from neighbours without a slot, +inf for domain voxels
+    without storage.  Exactly the bricks of the header's rule have a slot (stored / domain bricks, as observed: interior 36 / 135,
+    also with a float32 cost; reach 2 90 / 135; volume corners 16 / 135; brick corner seam 42 / 135; empty domain bricks
+    22 / 104; anisotropic 105 / 135) and every output equals the model's (_check's comparison, on the model kept by _sparse)."""
+    mask, cost, dom, spacing, max_cost, ref, stored, facts = _sparse(name)
+    b, info = _run(mask, cost, dom, None, spacing, max_cost, 0)
+    _same(b, info, ref)
+    assert info['bricks'] == int(stored.sum()) and info['bricks'] < facts['domain_bricks']
+    assert len(b) >= 1
+    _adjacent(b)
+    if name == 'interior':                                             # a domain voxel in a brick without storage: out of reach
+        assert not stored[0, 0, 0] and b.dist[2, 2, 2] == np.inf and b.root[2, 2, 2] == -1 and b.pred[2, 2, 2] == 255
+
+
+@pytest.mark.gpu
+def test_pair_table_wraps():
+    """The 64-entry table at exactly half its entries, every home in its last two (test_pair_table_certificate): probes run
+    past the last entry to entry 0, up to 31 steps long, and phase 2 finds after the same walk what phase 1 entered - a pair it
+    missed would come back with the tie word it was initialised with, and _same would see its (u, v)."""
+    mask, chosen, ref = _line(32)
+    b, info = _run(mask, np.ones(mask.shape), None, None, None, 4.0, 0)
+    _same(b, info, ref)
+    assert info['contacts'] == info['pairs'] == info['bridges'] == 32
+    assert b.pairs.tolist() == [[i, i + 1] for i in chosen]
+
+
+@pytest.mark.gpu
+def test_pair_table_grows_at_33_pairs():
+    """One pair more than half of 64 entries: the sizing loop takes its first step."""
+    mask, chosen, ref = _line(33)
+    b, info = _run(mask, np.ones(mask.shape), None, None, None, 4.0, 0)
+    _same(b, info, ref)
+
+
+@pytest.mark.gpu
+def test_second_call_after_the_capacity_error():
+    """More than 4096 bridges, fewer than 2^18 path entries: bridgeCandidates learns the sizes from the VRG_E_ARG of its first
+    call and runs again; nothing of the first call shows in the tables, the fields or the counts."""
+    mask, cost, ref = _lattice_36()
+    b, info = _run(mask, cost, None, None, None, 4.5, 0)
+    _same(b, info, ref)
+    assert len(b) > 4096 and len(b.voxels) < 1 << 18 and info['bridges'] == len(b)
 
 
 @pytest.mark.gpu
@@ -321,6 +516,24 @@ def _small():
     shape = (10, 10, 12)
     mask = _points(shape, [(2, 2, 2), (2, 2, 6), (6, 3, 2), (7, 7, 9)])
     return mask, np.random.default_rng(3).uniform(0.5, 1.5, shape)
+
+
+@pytest.mark.gpu
+def test_tip_rule_corners():
+    """tips == NULL counts every root as a tip, under rule 2 as well; all-zero tips leave rule 0 as it is and give rule 1
+    nothing: no contact although the flood reached voxels and every slot is there."""
+    mask, cost = _small()
+    ones, zeros = np.ones(mask.shape, np.uint8), np.zeros(mask.shape, np.uint8)
+    b1, info1, ref1 = _check(mask, cost, None, ones, None, 8.0, 2)
+    b0, info0, ref0 = _check(mask, cost, None, None, None, 8.0, 2)
+    assert len(b1) >= 3
+    _same(b0, info0, ref1)
+    b, info, ref = _check(mask, cost, None, zeros, None, 8.0, 1)
+    assert info['contacts'] == 0 and len(b) == 0 and b.offsets.tolist() == [0] and info['reached'] > 0 and info['bricks'] > 0
+    plain = BM.model(mask, cost, None, None, None, 8.0, 0)
+    b, info, ref = _check(mask, cost, None, zeros, None, 8.0, 0)
+    assert len(b) >= 3
+    _same(b, info, plain)
 
 
 @pytest.mark.gpu

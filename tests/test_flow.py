@@ -611,7 +611,13 @@ def test_main_writes_the_flow_files(tmp_path, capsys):
     assert '{} saved to {}.'.format(F.FLOW_FILE, os.path.join(str(solved), F.FLOW_FILE)) in said
     info_files = (S.SEGMENT_INFO_FILE, S.NODE_INFO_FILE)
     for name in os.listdir(str(plain)):                                   # every other file byte for byte
-        if name not in info_files:
+        if name == S.BRANCH_FILE:                                             # (but for labelRounds, which describes the run and differs between two)
+            with np.load(str(plain / name)) as x, np.load(str(solved / name)) as y:
+                assert x.files == y.files
+                for k in x.files:
+                    keep = x['countNames'] != 'labelRounds' if k == 'counts' else slice(None)
+                    assert x[k].dtype == y[k].dtype and np.array_equal(x[k][keep], y[k][keep]), (name, k)
+        elif name not in info_files:
             assert (plain / name).read_bytes() == (solved / name).read_bytes(), name
     assert all(np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b for a, b in zip(before, after))
     graph = S.branchGraph(S.skeletonize(m))
