@@ -214,6 +214,40 @@ def tube_lattice(shape, tubes):
     return cen, radius, min(amp, 0.18 * min(ny, nz))
 
 
+def digitise_curve(points):
+    """A voxel path from a fine sampling of a curve (float, N x 3, consecutive samples well under a voxel apart): every sample
+    rounded to its voxel, repeats dropped, and a voxel dropped whose two neighbours in the path are 26-adjacent (the corner of a
+    staircase that a thin skeleton would not keep).  Returns int64 M x 3: consecutive voxels are distinct 26-neighbours."""
+    out = []
+    for p in np.rint(np.asarray(points, np.float64)).astype(np.int64).tolist():
+        if out and p == out[-1]:
+            continue
+        while len(out) >= 2 and max(abs(a - b) for a, b in zip(out[-2], p)) <= 1:
+            out.pop()
+        if not out or p != out[-1]:
+            out.append(p)
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def arc_curve(radius, fraction=0.75, offset=(0.3, 0.45, 0.6), per_voxel=16):
+    """Samples of `fraction` of a circle of `radius` voxels in the plane of axes 1 and 2, its centre off the grid by `offset` and
+    far enough from 0 that every coordinate is positive; curvature 1 / radius.  Returns float64 N x 3."""
+    n = int(np.ceil(2 * np.pi * fraction * radius * per_voxel)) + 1
+    t = np.linspace(0.0, 2 * np.pi * fraction, n)
+    c = radius + 2.0
+    return np.stack([np.full(n, 2.0 + offset[0]), c + offset[1] + radius * np.cos(t), c + offset[2] + radius * np.sin(t)], axis=1)
+
+
+def helix_curve(radius, pitch=None, turns=1.5, offset=(0.3, 0.45, 0.6), per_voxel=16):
+    """Samples of a helix of `radius` voxels about axis 0 that climbs `pitch` voxels per radian (default radius / 3); curvature
+    radius / (radius^2 + pitch^2).  Returns float64 N x 3, every coordinate positive."""
+    c = radius / 3.0 if pitch is None else float(pitch)
+    n = int(np.ceil(2 * np.pi * turns * np.hypot(radius, c) * per_voxel)) + 1
+    t = np.linspace(0.0, 2 * np.pi * turns, n)
+    m = radius + 2.0
+    return np.stack([2.0 + offset[0] + c * t, m + offset[1] + radius * np.cos(t), m + offset[2] + radius * np.sin(t)], axis=1)
+
+
 def bench_volume_torch(shape, device, seed=3, levels=255, radius=4.0, noise=0.1, seed_planes=3, brain_mask=True, integer_values=False,
                        tubes=1, seed_mode='planes', brain_scale=0.48):
     """The configs 2-4 recipe generated directly in HBM with torch (plumbing only), x-fastest

@@ -7,7 +7,9 @@ volume derived from the vesselness, accepted when it is cheap enough; a ridge of
 follow, a jump sideways to a parallel vessel is not.  The flood, the contacts and the paths run in HIP; which bridges to take
 (`selectBridges`) is decided on the host.  No CPU path.
 
-Not claimed: the reference's spline geometry, its *Grow* and *Cut*, sub-voxel paths, bridges inside one component.
+Not claimed: the reference's spline geometry, its *Grow* and *Cut*, sub-voxel paths, bridges inside one component.  (A smooth
+sub-voxel curve through every branch of the graph - not through a bridge's path - is `skeletonization.branchSplines`, a smoothing
+spline of our own definition; the bridges themselves stay voxel paths.)
 """
 from __future__ import annotations
 

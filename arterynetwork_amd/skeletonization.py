@@ -53,6 +53,12 @@ writes ``partitionInfo.pkl`` and ``compartments.npz``.
 measured graph: the roots held at the inlet pressure, every reached end point at its terminal pressure, Hazen-Williams
 resistances from ``pathLength`` and ``meanRadius``; ``main(..., morphometry=True, roots=..., flow=dict(...))`` writes
 ``flowResult.npz`` and the ``simulationData`` entries of the two info files.
+
+``branchSplines`` (``vmask_centrelines``: DESIGN.md section 9, "f20 centreline splines") puts a smooth sub-voxel curve through every
+branch of that graph - a natural cubic smoothing spline per branch, its smoothing parameter searched per branch - and returns position,
+tangent, second derivative and curvature at every entry and the reference's three-point curvature statistic per branch
+(``graphRelated.calculateCurvature``); ``branchMorphometry(..., localDirection='spline')`` takes its local directions from it, and
+``main(..., prune=(3, 1.0), curvature=True)`` writes ``branchSplines.npz`` and the curvature keys of ``segmentInfoDict.pkl``.
 """
 from __future__ import annotations
 
@@ -123,6 +129,7 @@ def _skeleton_lib():
         dll.vmask_branches.argtypes = [C.c_int, p, i64, i64, i64, i64, C.c_double, p, i64, p, p, p, i64, p, p, i64, p, i64]
         dll.vmask_morphometry.argtypes = [C.c_int, i64, i64, i64, p, p, i64, p, p, p, i64, p, p, i64, i64, p, p, p, p, p, p, p, p, p]
         dll.vmask_compartments.argtypes = [C.c_int, i64, i64, i64, p, i64, p, p, p, i64, i64, p, p, p, p] + [p] * 10
+        dll.vmask_centrelines.argtypes = [C.c_int, i64, i64, i64, p, i64, p, p, C.c_double, C.c_double, C.c_double, C.c_double, i64, p, p, p, C.POINTER(C.c_double)]
     return dll
 
 
@@ -451,7 +458,9 @@ def _two_entry_radii(meanRadius, sigma, n, ends):
 def deriveMorphometry(raw, offsets, branchEnds, nodeKind, spacing):
     """The quantities that follow from vmask_morphometry's outputs by B- or N-sized numpy work; `raw` maps the names of
     `MORPHOMETRY_RAW` (and of `MORPHOMETRY_DEPTH`, or None) to host arrays.  Returns a dict with the names of `MORPHOMETRY_BRANCH` and
-    `MORPHOMETRY_BIFURCATION`; the formulas are those of `branchMorphometry`'s docstring."""
+    `MORPHOMETRY_BIFURCATION`; the formulas are those of `branchMorphometry`'s docstring.  An optional key ``localDirection`` of `raw`
+    (float64, B x 2 x 3: per branch end a direction from the node inwards, in the spacing's units) replaces ``endDir * spacing`` as
+    the local direction; everything after the direction is unchanged."""
     h = np.asarray(spacing, np.float64)
     off = np.asarray(offsets, np.int64)
     ends = np.asarray(branchEnds, np.int64).reshape(-1, 2)
@@ -476,7 +485,10 @@ def deriveMorphometry(raw, offsets, branchEnds, nodeKind, spacing):
     rows = np.flatnonzero((ib[:, 0] >= 0) & (n[np.maximum(ib, 0)] >= 3).all(axis=1)) if len(ib) and B else np.zeros(0, np.int64)
     K = len(rows)
     b3, e3 = ib[rows], ie[rows]                                           # K x 3, ascending branch index
-    local = raw['endDir'].reshape(-1, 2, 3)[b3, e3].astype(np.float64) * h             # K x 3 x 3: from the node inwards
+    if raw.get('localDirection') is not None:                             # (float directions per branch end, in the spacing's units)
+        local = np.asarray(raw['localDirection'], np.float64).reshape(-1, 2, 3)[b3, e3]
+    else:
+        local = raw['endDir'].reshape(-1, 2, 3)[b3, e3].astype(np.float64) * h         # K x 3 x 3: from the node inwards
     remote = (raw['chord'][b3] * np.where(e3 == 0, 1, -1)[..., None]).astype(np.float64) * h   # from the node to the far end
     with np.errstate(invalid='ignore', divide='ignore'):
         unit = local / _norm3(local)[..., None]
@@ -542,7 +554,110 @@ def _root_indices(roots, nodeCoords):
     return np.array(out, np.int64)
 
 
-def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roots=None, localSteps=5, device=0, info=None):
+SPLINE_FILE = 'branchSplines.npz'
+# the columns of vmask_centrelines' tables (include/vmask.h)
+SPLINE_ENTRY = ('u', 'position', 'second', 'tangent', 'curvature')
+SPLINE_BRANCH = ('smoothing', 'residual', 'splineLength', 'maxCurvature', 'meanCurvature', 'solves', 'capped', 'samples')
+_SPL_ENTRY, _SPL_F64, _SPL_INT = 11, 5, 3
+
+
+class BranchSplines:
+    """What `branchSplines` returns: one attribute per name of `SPLINE_ENTRY` (per entry of ``graph.coords``: ``u`` the parameter,
+    ``position``, ``second`` and ``tangent`` x 3, ``curvature``) and of `SPLINE_BRANCH` (per branch: ``smoothing`` the lambda used,
+    ``residual``, ``splineLength``, ``maxCurvature``, ``meanCurvature``, float64; ``solves``, ``capped``, ``samples``, int64); ``spacing``
+    and the parameters used: ``endWeight``, ``residualPerPoint``, ``sampleStep``, ``fixedSmoothing`` (None in search mode)."""
+
+    def names(self):
+        return list(SPLINE_ENTRY + SPLINE_BRANCH)
+
+
+def splineScale(spacing):
+    """``(l2, l, lambda_lo, lambda_hi)`` of a spacing: l2 = ((h0^2 + h1^2) + h2^2) / 3, l = sqrt(l2), and 2^-24, 2^24 times l2 l - the
+    range of the smoothing parameter.  The library forms the same four on the host."""
+    h = np.asarray(spacing, np.float64).reshape(3)
+    l2 = ((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2]) / 3.0
+    l = np.sqrt(l2)
+    l3 = l2 * l
+    return float(l2), float(l), float(l3 * 2.0 ** -24), float(l3 * 2.0 ** 24)
+
+
+def branchSplines(graph, spacing=None, smoothing=None, residualPerPoint=None, endWeight=20.0, sampleStep=None, device=0, info=None, ldsEntries=0):
+    """A smooth sub-voxel curve through every branch of a `BranchGraph` (``vmask_centrelines``, DESIGN.md section 9, "f20
+    centreline splines") as a `BranchSplines`: per branch the natural cubic smoothing spline (Reinsch) through its entries in
+    the parameter u = the cumulated step length in `spacing`, minimising sum_i w_i |y_i - f(u_i)|^2 + lambda int |f''|^2 du with
+    w = 1 and `endWeight` at the first and last entry.  include/vmask.h states every operation; the GPU equals
+    tests/centreline_model.py to the bit.
+    `smoothing` fixes lambda (inside the range of `splineScale`); the default searches, per branch, the largest lambda of 24
+    bisection steps on the geometric mean whose weighted residual is at most ``residualPerPoint * n`` (default 0.25 l2: an RMS
+    deviation of half a voxel per entry).  ``capped`` is 1 where the branch took lambda_hi (its least-squares line already meets the
+    target: every digitally straight branch, every branch of two entries), 2 where even lambda_lo misses it.  `sampleStep` (default
+    0.5 l) is the spacing of the resampling behind ``splineLength``, ``maxCurvature`` and ``meanCurvature`` - the three-point
+    curvature 4 S / (a b c) of the reference's ``curvature_by_triangle`` over consecutive samples; ``curvature`` per entry is the
+    analytic |f' x f''| / |f'|^3.  Positions are in the units of `spacing`, curvatures in their inverse.
+    A closed curve (first entry = last entry) is fitted as an OPEN curve with natural ends: no periodic spline.  FITPACK's knot
+    placement (``splprep(s=...)``, which the reference calls) is not reproduced; parity with it is not claimed.
+    A host graph gives host arrays, a graph of tensors on the GPU gives tensors on the same device.  `info`, when a dict, receives
+    ``capped`` (branches with a cap flag), ``solves`` (their total) and ``kernel_ms`` (the kernels' time by hipEvents).  `ldsEntries`
+    (0: the default of 256, at most 512) is the longest branch fitted in LDS; it changes no output bit.
+    ``ValueError``: a spacing that is not finite and positive or with max / min > 1000, `endWeight` or `sampleStep` not finite and
+    positive, `residualPerPoint` likewise, `smoothing` outside the range."""
+    h = np.ones(3, np.float64) if spacing is None else np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))
+    if not (np.isfinite(h).all() and (h > 0).all()) or h.max() / h.min() > 1000.0:
+        raise ValueError('spacing must be finite and positive with max / min <= 1000')
+    l2, l, lam_lo, lam_hi = splineScale(h)
+    if not (np.isfinite(endWeight) and endWeight > 0):
+        raise ValueError('endWeight must be finite and positive')
+    rho = 0.25 * l2 if residualPerPoint is None else float(residualPerPoint)
+    step = 0.5 * l if sampleStep is None else float(sampleStep)
+    if not (np.isfinite(rho) and rho > 0):
+        raise ValueError('residualPerPoint must be finite and positive')
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError('sampleStep must be finite and positive')
+    if smoothing is not None and not (np.isfinite(smoothing) and lam_lo <= float(smoothing) <= lam_hi):
+        raise ValueError('smoothing must lie in [{!r}, {!r}] (2^-24 .. 2^24 times l^3 of the spacing)'.format(lam_lo, lam_hi))
+    on_device = _G._on_device(graph.offsets)
+    shape = tuple(int(k) for k in graph.skeleton.shape)
+    n1, n2 = shape[1], shape[2]
+    B = int(graph.offsets.shape[0]) - 1
+    if on_device:
+        import torch
+        tdev = graph.offsets.device
+        dev = _G._dev_index(graph.offsets)
+        lin = lambda c: ((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2]).to(torch.int64).contiguous()
+        off = graph.offsets.to(torch.int64).contiguous()
+        alloc = lambda shp, dt: torch.empty(shp, dtype=torch.int64 if dt is np.int64 else torch.float64, device=tdev)
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        host = lambda a: a.cpu().numpy()
+        torch.cuda.synchronize(tdev)
+    else:
+        dev = device
+        lin = lambda c: np.ascontiguousarray((c[:, 0] * n1 + c[:, 1]) * n2 + c[:, 2], dtype=np.int64)
+        off = np.ascontiguousarray(graph.offsets, dtype=np.int64)
+        alloc = lambda shp, dt: np.empty(shp, dt)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        host = lambda a: a
+    vox = lin(graph.coords.reshape(-1, 3))
+    E = int(vox.shape[0])
+    ef, bf, bi = alloc((E, _SPL_ENTRY), np.float64), alloc((B, _SPL_F64), np.float64), alloc((B, _SPL_INT), np.int64)
+    ms = C.c_double(0.0)
+    _G._check(_skeleton_lib().vmask_centrelines(dev, *shape, ptr(off) if B else None, B, ptr(vox), h.ctypes.data, float(endWeight),
+                                                0.0 if smoothing is None else float(smoothing), rho, step, int(ldsEntries), ptr(ef), ptr(bf), ptr(bi), C.byref(ms)))
+    out = {'u': ef[:, 0], 'position': ef[:, 1:4], 'second': ef[:, 4:7], 'tangent': ef[:, 7:10], 'curvature': ef[:, 10],
+           'smoothing': bf[:, 0], 'residual': bf[:, 1], 'splineLength': bf[:, 2], 'maxCurvature': bf[:, 3], 'meanCurvature': bf[:, 4],
+           'solves': bi[:, 0], 'capped': bi[:, 1], 'samples': bi[:, 2]}
+    result = BranchSplines()
+    for k, v in out.items():
+        setattr(result, k, v.contiguous() if on_device else np.ascontiguousarray(v))
+    result.spacing, result.endWeight, result.residualPerPoint, result.sampleStep = h, float(endWeight), rho, step
+    result.fixedSmoothing = None if smoothing is None else float(smoothing)
+    if info is not None:
+        hbi = host(bi)
+        info['capped'], info['solves'], info['kernel_ms'] = int((hbi[:, 1] != 0).sum()), int(hbi[:, 0].sum()), float(ms.value)
+    return result
+
+
+def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roots=None, localSteps=5, device=0, info=None, localDirection='chord',
+                      splines=None):
     """The morphometry of a `BranchGraph` (``vmask_morphometry``, DESIGN.md section 9, "f11 branch morphometry") as a
     `BranchMorphometry`.  `dist` is the radius volume (default ``distance_transform_edt(vesselVolumeMask)``), `spacing` the voxel
     size per axis (default 1 1 1; positive, finite, max / min <= 1000), `roots` node indices or coordinate triples of node
@@ -580,7 +695,11 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     then ascend by branch index; otherwise, with the unit local directions u0, u1, u2 in ascending branch index, the first maximum
     of u0.u1, u1.u2, u2.u0 names the children - orders [0, 1, 2], [1, 2, 0], [2, 0, 1], the third being the parent
     (graphRelated.py:190-207).  THE LOCAL DIRECTION IS THE CHORD endDir * spacing OVER localSteps VOXELS, NOT THE REFERENCE'S
-    WEIGHTED SPLINE DERIVATIVE; the remote direction runs from the node's representative to the far end of the branch.
+    WEIGHTED SPLINE DERIVATIVE - UNLESS ``localDirection='spline'``: then it is the unit tangent of `branchSplines` at the branch's
+    first entry for end 0 and minus the tangent at its last entry for end 1 (both point into the branch), `splines` being a
+    `BranchSplines` of this graph (default ``branchSplines(graph, spacing=spacing)``: end weight 20, as the reference weights the
+    ends for this purpose).  That is a smoothing-spline derivative of our own definition, not FITPACK's; ``'chord'``, the default,
+    returns what it always did.  The remote direction runs from the node's representative to the far end of the branch.
     local / remoteBifurcationAmplitude: the angle between the children's directions, degrees, from the clipped cosine;
     local / remoteBifurcationTilt: the angle between the children's half-angle vector (sum of the unit directions) and minus the
     parent's local direction, NaN when that vector's norm is <= 1e-4; cubicLawResult = (r1^3 + r2^3) / r3^3, squareLawResult
@@ -589,6 +708,8 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
     whose two ends are both in the table, else NaN): the angle between the two normals, folded to at most 90 degrees."""
     if int(localSteps) < 1:
         raise ValueError('localSteps must be at least 1')
+    if localDirection not in ('chord', 'spline'):
+        raise ValueError('localDirection is \'chord\' or \'spline\'')
     on_device = _G._on_device(graph.offsets)
     shape = tuple(int(k) for k in graph.skeleton.shape)
     if dist is None:
@@ -645,8 +766,18 @@ def branchMorphometry(graph, dist=None, vesselVolumeMask=None, spacing=None, roo
         k = int(np.flatnonzero(interior)[0])
         raise ValueError('branch {} has {} pairs of consecutive entries inside it that are no 26-neighbours ({} such pairs in the table): pathLength leaves '
                          'them out, so the table is refused'.format(k, int(interior[k]), int(interior.sum())))
+    if localDirection == 'spline':
+        if splines is None:
+            splines = branchSplines(graph, spacing=spacing, device=device)
+        tangent = splines.tangent
+        tangent = np.asarray(tangent.cpu().numpy() if _G._on_device(tangent) else tangent, np.float64).reshape(-1, 3)
+        if len(tangent) != int(vox.shape[0]):
+            raise ValueError('splines does not belong to this graph: {} entries, the graph has {}'.format(len(tangent), int(vox.shape[0])))
+        hoff = host(off)
+        hraw = dict(hraw, localDirection=np.stack([tangent[hoff[:-1]], -tangent[hoff[1:] - 1]], axis=1).reshape(B, 2, 3))
     derived = deriveMorphometry(hraw, host(off), host(ends), host(graph.nodeKind), h)
     result = BranchMorphometry()
+    result.localDirection = localDirection
     for k in MORPHOMETRY_DEPTH:
         setattr(result, k, None)
     for k, v in raw.items():
@@ -662,7 +793,17 @@ def _plain(x):
     return x.tolist() if hasattr(x, 'tolist') else x
 
 
-def writeMorphometry(graph, measured, baseFolder, parts=None):
+def writeSplines(splines, baseFolder):
+    """``branchSplines.npz`` for a host `BranchSplines`: every array of ``splines.names()``, ``names``, ``spacing``, ``endWeight``,
+    ``residualPerPoint``, ``sampleStep`` and ``fixedSmoothing`` (NaN in search mode); returns the file's name."""
+    s = splines
+    np.savez_compressed(os.path.join(baseFolder, SPLINE_FILE), names=np.array(s.names()), spacing=s.spacing, endWeight=np.float64(s.endWeight),
+                        residualPerPoint=np.float64(s.residualPerPoint), sampleStep=np.float64(s.sampleStep),
+                        fixedSmoothing=np.float64(np.nan if s.fixedSmoothing is None else s.fixedSmoothing), **{k: getattr(s, k) for k in s.names()})
+    return SPLINE_FILE
+
+
+def writeMorphometry(graph, measured, baseFolder, parts=None, splines=None):
     """The files of ``main(..., morphometry=True)`` for a host `BranchGraph` and its `BranchMorphometry`; returns their names.
     ``branchMorphometry.npz``: every array of ``measured.names()``, ``names``, ``spacing``, ``localSteps``, ``roots``.
     ``graphRepresentationWithEdgeInfo.graphml``: the graph of `writeGraphml` with the edge attributes pathLength, eculideanLength,
@@ -672,7 +813,11 @@ def writeMorphometry(graph, measured, baseFolder, parts=None):
     (keyed by coordinate tuple: every node representative) with the reference's key names and plain Python values, pickle
     protocol 2: per entry the keys that `calculateProperty` writes and no others - a branch of two entries has no ``sigma``, and
     ``segmentLevel`` comes from a partition alone.  With `parts` (a `Compartments` of host arrays) the entries of owned branches and
-    nodes gain ``partitionName``, and the segments ``segmentLevel`` - the partition's, as graphRelated.py:72-74,108-110 reads them."""
+    nodes gain ``partitionName``, and the segments ``segmentLevel`` - the partition's, as graphRelated.py:72-74,108-110 reads them.
+    With `splines` (a host `BranchSplines` of this graph) every segment's entry gains ``maxCurvature``, ``meanCurvature`` and
+    ``splineLength``, and the first two again under ``maxCurvatureAveragedInmm`` / ``meanCurvatureAveragedInmm``, the names the
+    reference's plotting code reads - here PER BRANCH and in 1 / unit of the spacing, where the reference averages over its
+    root-to-terminal path fits.  Without `splines` the files are byte for byte what they were."""
     import pickle
     m = measured
     names = m.names()
@@ -731,6 +876,9 @@ def writeMorphometry(graph, measured, baseFolder, parts=None):
             d['localBifurcationTorque'] = float(m.localBifurcationTorque[k])
         if parts is not None and parts.branchCompartment[k]:
             d['partitionName'], d['segmentLevel'] = parts.names[int(parts.branchCompartment[k]) - 1], int(parts.branchLevel[k])
+        if splines is not None:
+            d['maxCurvature'], d['meanCurvature'], d['splineLength'] = (float(getattr(splines, key)[k]) for key in ('maxCurvature', 'meanCurvature', 'splineLength'))
+            d['maxCurvatureAveragedInmm'], d['meanCurvatureAveragedInmm'] = d['maxCurvature'], d['meanCurvature']
         segment_info[k] = d
     node_info = {}
     kinds, degrees = _plain(graph.nodeKind), _plain(graph.nodeDegree)
@@ -1153,7 +1301,8 @@ def _add_simulation_data(graph, result, extra, baseFolder):
             pickle.dump(info, f, protocol=2)
 
 
-def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None, flow=None):
+def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None, flow=None,
+         curvature=False):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -1186,9 +1335,16 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     ``c``, and optionally ``k``, ``metresPerUnit`` (default 1e-3: the affine is in millimetres), ``factor``, ``inlet``, ``tol``,
     ``maxIter``.  ``flowResult.npz`` (the `FlowResult` and `flowOnGraph`'s extras) is written, and the entries of
     ``segmentInfoDict.pkl`` / ``nodeInfoDict.pkl`` gain ``simulationData`` with ``velocity`` and ``flow`` / ``pressure``.  The
-    returned values are those of a run without it; without `flow` every file is byte for byte what it was."""
+    returned values are those of a run without it; without `flow` every file is byte for byte what it was.
+    With ``curvature=True`` as well (it needs `prune`): `branchSplines` in the affine's spacing with its defaults, written as
+    ``branchSplines.npz`` (`writeSplines`); with ``morphometry=True`` the entries of ``segmentInfoDict.pkl`` gain ``maxCurvature``,
+    ``meanCurvature``, ``splineLength`` and the first two under the reference's ``maxCurvatureAveragedInmm`` /
+    ``meanCurvatureAveragedInmm`` (`writeMorphometry`).  The returned values are those of a run without it; without `curvature`
+    every file is byte for byte what it was."""
     if flow is not None and (not morphometry or roots is None):
         raise ValueError('flow needs morphometry=True and roots')
+    if curvature and prune is None:
+        raise ValueError('curvature=True needs prune (prune=(0, 0.0) prunes nothing)')
     if compartments is not None and prune is None:
         raise ValueError('compartments needs prune (prune=(0, 0.0) prunes nothing)')
     if morphometry and prune is None:
@@ -1235,10 +1391,18 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
             with open(compartments, 'rb') as f:
                 compartments = pickle.load(f)
         parts = partitionCompartments(graph, compartments)
+    extra = {}
+    if curvature:
+        spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
+        extra['splines'] = branchSplines(graph, spacing=spacing)
+        name = writeSplines(extra['splines'], baseFolder)
+        print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if morphometry:
         spacing = np.sqrt((np.asarray(affine, dtype=np.float64)[:3, :3] ** 2).sum(axis=0))
         measured = branchMorphometry(graph, vesselVolumeMask=vesselVolumeMask, spacing=spacing, roots=roots)
-        for name in (writeMorphometry(graph, measured, baseFolder) if parts is None else writeMorphometry(graph, measured, baseFolder, parts=parts)):
+        if parts is not None:
+            extra['parts'] = parts
+        for name in writeMorphometry(graph, measured, baseFolder, **extra):
             print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if flow is not None:
         from . import flow as _flow

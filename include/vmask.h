@@ -377,6 +377,66 @@ int vmask_compartments(int device, int64_t n0, int64_t n1, int64_t n2,
                        uint8_t* branch_comp, int64_t* branch_level,                          /* nbranch each */
                        int64_t* comp_counts /* (ncomp + 1) x 3 */, int64_t* counts /* 2, may be NULL */);
 
+/* Centreline splines: one natural cubic smoothing spline (Reinsch) per branch, the three coordinates sharing one matrix.  The
+ * shape of the volume and the branch table of vmask_branches: offsets[nbranch + 1], voxels[E], E = offsets[nbranch] (C-order
+ * linear indices); spacing (h0, h1, h2; NULL: 1 1 1; host or device).  Every operation below is one IEEE double operation in the
+ * order written, nothing contracted into an FMA, no floating-point atomics, division and square root correctly rounded.
+ * |x| = sqrt((x0^2 + x1^2) + x2^2).  Branch b has n >= 2 entries e_0 .. e_(n-1) (voxel coordinates):
+ *   y_i = (e_i - e_0) h per axis (the integer difference, then one product);  u_0 = 0, u_(i+1) = u_i + |y_(i+1) - y_i|;
+ *   hh_i = u_(i+1) - u_i, r_i = 1 / hh_i;  w_0 = w_(n-1) = end_weight, w_i = 1 elsewhere, v_i = 1 / w_i.
+ * The curve f minimises sum_i w_i |y_i - f(u_i)|^2 + lambda int |f''|^2 du over the natural cubic splines with knots u_i.  With
+ * mu = 1 / lambda, m = n - 2, Q (n x m: column j = (r_j, -(r_j + r_(j+1)), r_(j+1)) in rows j, j + 1, j + 2) and R (m x m:
+ * R_jj = (hh_j + hh_(j+1)) / 3, R_(j,j+1) = hh_(j+1) / 6) it solves the scaled system (mu R + Q' W^-1 Q) c = Q' y; g = y - W^-1 Q c are the
+ * fitted positions, gamma = mu c (0 at both ends) the second derivatives at the knots.  For j in [0, m), s_j = r_j + r_(j+1):
+ *   a0_j = ((r_j r_j) v_j + (s_j s_j) v_(j+1)) + (r_(j+1) r_(j+1)) v_(j+2)
+ *   a1_j = -((s_j r_(j+1)) v_(j+1) + (r_(j+1) s_(j+1)) v_(j+2)) for j < m - 1;  a2_j = (r_(j+1) r_(j+2)) v_(j+2) for j < m - 2
+ *   R0_j = (hh_j + hh_(j+1)) / 3, R1_j = hh_(j+1) / 6;  b_j = (y_(j+2) - y_(j+1)) r_(j+1) - (y_(j+1) - y_j) r_j per axis (this is Q' y)
+ *   d0 = mu R0 + a0, d1 = mu R1 + a1, d2 = a2, factored L D L' by the forward recurrence, with L2_i = 0 for i < 2, L1_0 = 0, and 1
+ *   for a D, 0 for a z' or c outside [0, m):
+ *     L2_i = d2_(i-2) / D_(i-2);  L1_i = (d1_(i-1) - (L2_i D_(i-2)) L1_(i-1)) / D_(i-1);  D_i = (d0_i - (L1_i L1_i) D_(i-1)) - (L2_i L2_i) D_(i-2)
+ *     z'_i = (b_i - L1_i z'_(i-1)) - L2_i z'_(i-2);  z_i = z'_i / D_i;  then downwards c_i = (z_i - L1_(i+1) c_(i+1)) - L2_(i+2) c_(i+2)
+ *   q_i = r_(i-1) (c_(i-2) - c_(i-1)) + r_i (c_i - c_(i-1)) per axis, an r or c outside its range being 0 (this is (Q c)_i);
+ *   e_i = v_i q_i, g_i = y_i - e_i, gamma_i = mu c_(i-1) for 0 < i < n - 1.
+ *   The residual F(lambda) = the ORDERED SUM that vmask_morphometry states, of x_i = w_i ((e_i0^2 + e_i1^2) + e_i2^2), i = 0 .. n - 1.
+ * n = 2 has no unknown: g = y, gamma = 0, F = 0.  n = 3 and 4 go through the same formulas (m = 1, 2).  A closed curve (first
+ * entry = last entry) is fitted as an open curve with natural ends; no periodic spline.
+ * LAMBDA.  l2 = ((h0^2 + h1^2) + h2^2) / 3, l = sqrt(l2), lambda_lo = 2^-24 (l2 l), lambda_hi = 2^24 (l2 l), on the host.
+ *   smoothing > 0: lambda = smoothing (inside [lambda_lo, lambda_hi]); solves = 1, capped = 0.
+ *   smoothing <= 0: the target is S = residual_per_point n.  F(lambda_hi) <= S, or n = 2: lambda = lambda_hi, solves = 1, capped = 1.
+ *   Otherwise lo = lambda_lo, hi = lambda_hi and 24 times: mid = sqrt(lo hi); F(mid) > S ? hi = mid : lo = mid.  lambda = lo, solves =
+ *   25 (the trial values; the fit at lambda is one more solve); capped = 2 when no trial moved lo and F(lambda_lo) > S, else 0.
+ * entry_f64 (E x 11): [0] u_i; [1..3] position (e_0 h) + g_i; [4..6] the second derivative gamma_i; [7..9] the unit tangent d_i / |d_i|
+ *   of the first derivative d_i = (g_(i+1) - g_i) / hh_i - (hh_i (2 gamma_i + gamma_(i+1))) / 6 on the right of knot i < n - 1, and at the last
+ *   entry, with k = n - 2, (g_(k+1) - g_k) / hh_k + (hh_k (gamma_k + 2 gamma_(k+1))) / 6; [10] the curvature |d x gamma| / ((|d| |d|) |d|), the cross
+ *   product being (d1 s2 - d2 s1, d2 s0 - d0 s2, d0 s1 - d1 s0).  A NaN is stored as 0x7ff8000000000000.
+ * branch_f64 (nbranch x 5): [0] lambda, [1] the residual F(lambda), [2] splineLength, [3] maxCurvature, [4] meanCurvature.
+ * branch_int (nbranch x 3): [0] solves, [1] capped, [2] samples.
+ * THE SAMPLES.  U = u_(n-1); M = max(3, ceil(U / sample_step) + 1) samples at u_k = (k U) / (M - 1) for k < M - 1 and u_(M-1) = U.
+ *   THE CUBIC at a parameter x: i = the last knot of 0 .. n - 2 with u_i <= x, t = x - u_i,
+ *     P = g_i + t (d_i + t (0.5 gamma_i + t ((gamma_(i+1) - gamma_i) / (6 hh_i))))   per axis (centred on e_0 h, which no difference needs).
+ *   chord_k = |P_(k+1) - P_k|, k in [0, M - 1): splineLength = their ordered sum.  Triangle k in [0, M - 2) of P_k, P_(k+1), P_(k+2): the sides
+ *   |P_k - P_(k+1)|, |P_k - P_(k+2)|, |P_(k+1) - P_(k+2)| sorted a >= b >= c, t = (((a + (b + c)) (c - (a - b))) (c + (a - b))) (a + (b - c)),
+ *   kappa_k = (t > 0 ? sqrt(t) : 0) / ((a b) c) - the 4 S / (a b c) of the reference's curvature_by_triangle, S = 0 where t < 0.  maxCurvature = the
+ *   maximum (fmax from 0), meanCurvature = the ordered sum of kappa_0 .. kappa_(M-3), divided by M - 2.
+ * lds_entries: the longest branch whose work arrays (15 doubles per entry) are kept in LDS, 0 = 256, at most 512; a longer
+ * branch runs the same code over a global work space.  Every output is a pure function of the other inputs, bit-identical
+ * between runs and whatever lds_entries is.  kernel_ms (host, may be NULL): the time of the kernels by hipEvents - it
+ * describes the run, not the result.
+ * VRG_E_ARG, before anything is written: the spacing rules of vmask_morphometry; end_weight not finite and positive; a NaN
+ * smoothing or one > 0 outside [lambda_lo, lambda_hi]; in search mode a residual_per_point not finite and positive; sample_step
+ * not finite or below 2^-10 l; lds_entries outside [0, 512]; offsets that do not start at 0 or leave a branch fewer than two
+ * entries, a voxel outside the volume, two consecutive entries of a branch on the same voxel - a zero step - (counted on the
+ * device); a shape outside the envelope of the other passes.  nbranch = 0 succeeds and writes nothing.
+ * VRG_E_MEM: the tables and outputs where they are host arrays, and - only when a branch is longer than lds_entries - 120 bytes
+ * per entry do not fit the device; everything allocated is freed. */
+int vmask_centrelines(int device, int64_t n0, int64_t n1, int64_t n2,
+                      const int64_t* offsets, int64_t nbranch, const int64_t* voxels,
+                      const double* spacing /* may be NULL */, double end_weight,
+                      double smoothing /* > 0: fixed lambda; <= 0: search */, double residual_per_point, double sample_step,
+                      int64_t lds_entries /* 0: default */,
+                      double* entry_f64 /* E x 11 */, double* branch_f64 /* nbranch x 5 */, int64_t* branch_int /* nbranch x 3 */,
+                      double* kernel_ms /* may be NULL */);
+
 /* The flow solve on the branch graph: S >= 1 scenarios of one topology in one launch.  The graph is vmask_branches': nnode nodes,
  * nbranch branches with branch_ends[2 nbranch].  A branch with ends -1 -1 (a closed curve) or with both ends on one node (a
  * loop) carries no flow: Q = 0, it takes no part.  Parallel branches are ordinary.
