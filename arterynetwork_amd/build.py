@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libvrg_hip.so')
-SOURCES = ['vrg_chain.hip', 'vrg_device.hip', 'vrg_init.hip', 'vrg_follow.hip', 'vmask_device.hip', 'vskel_device.hip', 'vrg_engine.cpp', 'vseg_device.hip', 'vves_device.hip', 'vter_device.hip', 'vgeo_device.hip', 'vbr_device.hip', 'vmor_device.hip', 'vcl_device.hip', 'vcomp_device.hip', 'vflow_device.hip', 'vden_device.hip', 'vbias_device.hip', 'vreg_device.hip', 'vbrain_device.hip', 'vwarp_device.hip', 'vbridge_device.hip']
+SOURCES = ['vrg_chain.hip', 'vrg_device.hip', 'vrg_init.hip', 'vrg_follow.hip', 'vmask_device.hip', 'vskel_device.hip', 'vrg_engine.cpp', 'vseg_device.hip', 'vves_device.hip', 'vter_device.hip', 'vgeo_device.hip', 'vbr_device.hip', 'vmor_device.hip', 'vcl_device.hip', 'vcomp_device.hip', 'vflow_device.hip', 'vden_device.hip', 'vbias_device.hip', 'vreg_device.hip', 'vbrain_device.hip', 'vwarp_device.hip', 'vbridge_device.hip', 'vtube_device.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17']
 
 

@@ -59,6 +59,10 @@ branch of that graph - a natural cubic smoothing spline per branch, its smoothin
 tangent, second derivative and curvature at every entry and the reference's three-point curvature statistic per branch
 (``graphRelated.calculateCurvature``); ``branchMorphometry(..., localDirection='spline')`` takes its local directions from it, and
 ``main(..., prune=(3, 1.0), curvature=True)`` writes ``branchSplines.npz`` and the curvature keys of ``segmentInfoDict.pkl``.
+
+``tubes.graphTubes`` (``vmask_tubes``: DESIGN.md section 9, "f21 tube model") is the way back from that graph to the voxels: the centre points
+and radii rasterised to a label volume with per-branch voxel counts and their overlap with the mask;
+``main(..., prune=(3, 1.0), morphometry=True, tubes=True)`` writes ``vesselVolumeModel.nii.gz``, ``branchLabelsModel.nii.gz`` and ``tubeModel.npz``.
 """
 from __future__ import annotations
 
@@ -1302,7 +1306,7 @@ def _add_simulation_data(graph, result, extra, baseFolder):
 
 
 def main(baseFolder=None, segments=False, territories=False, geodesic=False, prune=None, morphometry=False, roots=None, compartments=None, flow=None,
-         curvature=False):
+         curvature=False, tubes=None):
     """File-level equivalent of what the reference's skeleton stage leaves behind (:771-790): the skeleton of
     ``vesselVolumeMask.nii.gz`` as ``skeleton.nii.gz`` (uint8, the mask's affine) in the same folder; returns the skeleton.
     With ``segments=True`` also ``segmentList.npz`` and ``graphRepresentation.graphml`` beside it; returns
@@ -1340,7 +1344,15 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
     ``branchSplines.npz`` (`writeSplines`); with ``morphometry=True`` the entries of ``segmentInfoDict.pkl`` gain ``maxCurvature``,
     ``meanCurvature``, ``splineLength`` and the first two under the reference's ``maxCurvatureAveragedInmm`` /
     ``meanCurvatureAveragedInmm`` (`writeMorphometry`).  The returned values are those of a run without it; without `curvature`
-    every file is byte for byte what it was."""
+    every file is byte for byte what it was.
+    With `tubes` as well (``True`` or a dict; it needs `prune` and ``morphometry=True``): the tube model of the branch graph
+    (`tubes.graphTubes`: DESIGN.md section 9, "f21 tube model") in the affine's spacing, compared with the mask - the centre points
+    being the splines' when ``curvature=True``, the voxel centres otherwise; a dict may give ``minRadius``, ``radiusScale`` and
+    ``keep``.  ``vesselVolumeModel.nii.gz`` (uint8), ``branchLabelsModel.nii.gz`` (int32: branch k has label k + 1) and
+    ``tubeModel.npz`` (`tubes.writeTubes`) are written, with `flow` also ``branchFlow.nii.gz`` (float32: |flow| of the branch that
+    holds the voxel).  The returned values are those of a run without it; without `tubes` every file is byte for byte what it was."""
+    if tubes is not None and tubes is not False and (prune is None or not morphometry):
+        raise ValueError('tubes needs prune and morphometry=True (prune=(0, 0.0) prunes nothing)')
     if flow is not None and (not morphometry or roots is None):
         raise ValueError('flow needs morphometry=True and roots')
     if curvature and prune is None:
@@ -1404,12 +1416,19 @@ def main(baseFolder=None, segments=False, territories=False, geodesic=False, pru
             extra['parts'] = parts
         for name in writeMorphometry(graph, measured, baseFolder, **extra):
             print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
+    splines = extra.get('splines')
+    solved = None
     if flow is not None:
         from . import flow as _flow
         solved, extra = flowOnGraph(graph, measured, spacing, **flow)
         _add_simulation_data(graph, solved, extra, baseFolder)
         name = _flow.writeFlow(solved, baseFolder, **extra)
         print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
+    if tubes is not None and tubes is not False:
+        from . import tubes as _tubes
+        model = _tubes.graphTubes(graph, measured, splines=splines, spacing=spacing, mask=vesselVolumeMask, **(tubes if isinstance(tubes, dict) else {}))
+        for name in _tubes.writeTubes(model, baseFolder, affine, measured=measured, flow=None if solved is None else solved.flow[0]):
+            print('{} saved to {}.'.format(name, os.path.join(baseFolder, name)))
     if parts is not None:
         compartmentSizes = None
         if territories:

@@ -106,6 +106,15 @@
  *                      tests/bridge_model.py, which a heap Dijkstra beside it confirms; bit-identical repeats.  Not claimed: the
  *                      reference's spline geometry, its Grow and Cut, sub-voxel paths, bridges inside one component; which
  *                      bridges to take is the Python layer's decision (reconnect.selectBridges).
+ *   vmask_tubes        the way back from the graph to the voxels: the reference's manual-correction step edits centre lines only
+ *                      ("the ability to directly modify the 3D segmentation volume might be added in the future") and gives a
+ *                      branch's volume only as a cylinder (getVolumePerPartition, fluidSimulation.py:814-842); vmask_territories
+ *                      and vmask_geodesic label the voxels of a given mask.  Here the branch table itself - sub-voxel centre points
+ *                      and radii - is rasterised: every voxel gets the branch whose swept ball it lies deepest in, every branch its
+ *                      voxel count and how many of them a given mask has; DESIGN.md section 9, f21.  Claimed: exact equality - the
+ *                      bits of label, field, nearest, every count - with the brute-force model tests/tube_model.py, the tie rule
+ *                      included; bit-identical repeats.  Not claimed: anti-aliased (partial-volume) voxels, any treatment of
+ *                      junctions beyond the union of the tubes, the reference's cylinder volumes, any smoothing of the radii.
  *
  * All arrays are dense C-order [n0][n1][n2] (the caller's own axis order; numbering of components
  * follows that raster order exactly as skimage / scipy do).  Pointers may be host or device pointers.
@@ -436,6 +445,57 @@ int vmask_centrelines(int device, int64_t n0, int64_t n1, int64_t n2,
                       int64_t lds_entries /* 0: default */,
                       double* entry_f64 /* E x 11 */, double* branch_f64 /* nbranch x 5 */, int64_t* branch_int /* nbranch x 3 */,
                       double* kernel_ms /* may be NULL */);
+
+/* The tube model: a branch table with centre points and radii rasterised to a volume of n0 x n1 x n2 voxels (fewer than 2^31).
+ * INPUTS.  spacing h (h0, h1, h2; NULL: 1 1 1; the rules of vmask_centrelines: finite, positive, max / min <= 1000).  The branch
+ * table offsets[nbranch + 1]: it starts at 0 and every branch has at least two entries (so it does not decrease); E = offsets[nbranch]
+ * < 2^31.  P (E x 3 float64): the centre points in the units of the spacing - voxel (i0, i1, i2) sits at (i0 h0, i1 h1, i2 h2).
+ * r (E float64): the radii in the same units.  keep (nbranch uint8, may be NULL): a branch with 0 contributes nothing.
+ * branch_label (nbranch int32, > 0; NULL: b + 1).  mask (uint8 volume, may be NULL).
+ * PRIMITIVES.  Primitive e joins the consecutive entries e and e + 1 of one branch (A = P[e], B = P[e + 1], rA = r[e], rB = r[e + 1]):
+ * the segment A B swept by a ball whose radius runs linearly from rA to rB.  At voxel i, in float64, every operation rounded on
+ * its own (nothing contracted into an FMA), the sums in the order written, per axis a:
+ *   x_a = fl(i_a h_a)
+ *   d_a = B_a - A_a                 dd = (d0 d0 + d1 d1) + d2 d2
+ *   w_a = x_a - A_a                 wd = (w0 d0 + w1 d1) + w2 d2
+ *   t   = 0 if dd == 0 else min(max(wd / dd, 0), 1), taken as: t = wd / dd; t = t if t > 0 else 0; t = 1 if t > 1 else t (a NaN gives 0)
+ *   c_a = A_a + t d_a               q_a = x_a - c_a
+ *   qq  = (q0 q0 + q1 q1) + q2 q2
+ *   rho = rA + t (rB - rA)          f = qq - rho rho
+ * wd / dd is the correctly rounded division, never a reciprocal.  The voxel is INSIDE primitive e iff f <= 0.  f is the power
+ * distance to the swept ball at the foot point: where two vessels overlap, a voxel goes to the one it lies deeper in, as in a
+ * power diagram.
+ * PER VOXEL.  Over the primitives of kept branches with f <= 0 the lexicographically least pair (f, e) wins:
+ *   label (int32): the label of e's branch, 0 when there is none;  field (float64, may be NULL): that f, +inf when there is none;
+ *   nearest (int64, may be NULL): that e, -1 when there is none.
+ * PER CALL.  sizes[nbranch] (int64): the voxels whose winner belongs to branch b;  overlap[nbranch]: those of them with mask != 0
+ * (all 0 without a mask);  missed (1): the voxels with mask != 0 and label 0;  counts (4, may be NULL): the primitives of kept
+ * branches, the occupied bricks, the (brick, primitive) pairs, the longest brick list.  Every count comes from integer atomics and
+ * every other output is a minimum over a set: repeats are bit-identical.
+ * THE RUN (it describes the run, no output bit depends on it).  The volume is cut into the 8 x 8 x 8 bricks of the floods.  Per
+ * primitive an index box: per axis from floor(min(A_a - rA, B_a - rB) / h_a) - 1 to ceil(max(A_a + rA, B_a + rB) / h_a) + 1, clipped
+ * to the volume.  c_a - rho and c_a + rho are linear in t, so in exact arithmetic every voxel with f <= 0 lies in the box without
+ * the extra voxel; the rounding of x, c and rho moves a bound by less than 2^-30 of the largest spacing - the inputs are at most
+ * 2^20 of it - which is less than 2^-20 voxels at the spacing ratio allowed, and the box is one whole voxel wider.  The bricks
+ * that a box meets are counted, scanned and filled into per-brick lists (order free: the winner rule does not see it); one workgroup
+ * of 512 threads per occupied brick evaluates its list, a wave skipping a primitive whose box misses its slice; the bricks with an
+ * empty list are filled with 0, +inf, -1.  A call in which no brick is occupied (nbranch = 0, every branch dropped, everything
+ * outside the volume) launches no empty grid and returns zeros, +inf and -1.
+ * step_ms (6, host, may be NULL): the time by hipEvents of the table check, the count pass, the scan, the list fill, the evaluation
+ * and the fill of the empty bricks.
+ * VRG_E_ARG, before anything is written: a spacing outside the rules; offsets that do not start at 0 or leave a branch fewer than
+ * two entries, E >= 2^31; a coordinate or radius that is not finite; a negative radius; |P_a| or r above 2^20 max(h); a label <= 0
+ * (all counted on the device, over every branch whether kept or not); more than 2^31 - 1 (brick, primitive) pairs, with a text
+ * that says so; a shape outside the envelope of the other passes; a NULL label or missed.  nbranch = 0 is no error.
+ * VRG_E_MEM: the tables and outputs where they are host arrays, 4 bytes per entry, 8 per brick and 4 per pair do not fit the
+ * device; everything allocated is freed. */
+int vmask_tubes(int device, int64_t n0, int64_t n1, int64_t n2, const double* spacing /* may be NULL */,
+                const int64_t* offsets, int64_t nbranch, const double* positions /* E x 3 */, const double* radius /* E */,
+                const uint8_t* keep /* nbranch, may be NULL */, const int32_t* branch_label /* nbranch, may be NULL */,
+                const uint8_t* mask /* may be NULL */,
+                int32_t* label, double* field /* may be NULL */, int64_t* nearest /* may be NULL */,
+                int64_t* sizes /* nbranch */, int64_t* overlap /* nbranch */, int64_t* missed /* 1 */,
+                int64_t* counts /* 4, may be NULL */, double* step_ms /* 6, host, may be NULL */);
 
 /* The flow solve on the branch graph: S >= 1 scenarios of one topology in one launch.  The graph is vmask_branches': nnode nodes,
  * nbranch branches with branch_ends[2 nbranch].  A branch with ends -1 -1 (a closed curve) or with both ends on one node (a
